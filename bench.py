@@ -7,8 +7,16 @@
 
 A "step" is one qps_solve() of --iters ADMM iterations (default 500; ϵAbs = ϵRel = 0 so exactly that many run) on a problem already
 resident in HBM with its factorisation cached (setup is reported separately).  Rank 0 prints ONE JSON line carrying
-`roofline` (dominant kernel, HIP events attached to its dispatches on the solver's stream, inside the timed region) and
-`cpu_baseline` (the oracle's C restatement on this box's host cores, bounded sample; rank 0 at N = 1 only).
+`ms_per_step` (wall time of one timed step, slowest rank) and `roofline` (dominant kernel, HIP events attached to its dispatches on the
+solver's stream, inside the timed region).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the legs that take runs of their own, after the
+timed region: `cpu_baseline` + `parity` (the oracle's C restatement on the host cores, bounded sample; rank 0 at N = 1 only),
+`time_to_eps` (c2 / c5 / c4) and, for the default command, `side_configs` (the GPU legs of c5 / c4 / c3); --no-cpu-baseline,
+--no-time-to-eps and --no-side-configs switch single legs of a --full run off.
+
+--dump-outputs DIR writes rank 0's result of the last timed step as float64 .npy files: x.npy, z.npy, y.npy (batch c4: one row per QP
+of the rank).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import csv
@@ -73,6 +81,10 @@ def main():
     ap.add_argument("--iters", type=int, default=0, help="ADMM iterations per step (default 500; 100 for c3 / c4; 2000 for c1)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--trsv-block", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline + parity, time-to-eps and (default command) side-config legs after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x / z / y of the last timed step (rank 0) as float64 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-time-to-eps", action="store_true")
     ap.add_argument("--no-side-configs", action="store_true",
@@ -82,6 +94,8 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="rank plumbing only (rendezvous, barrier, timing reduction) with a sleep in place of the solver: runs without a GPU")
     args = ap.parse_args()
+    if not args.full:          # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_time_to_eps = args.no_side_configs = True
     spawn_ranks_if_needed(args, sys.argv[1:])
 
     import torch  # first: keeps a single HIP runtime in the process (torch bundles its own libamdhip64)
@@ -115,8 +129,25 @@ def main():
         out["config"]["dist_backend"] = backend
         out["config"]["ranks"] = info.world_size
         out["config"]["devices_visible"] = ndev
+        out["config"]["full"] = args.full
         print(json.dumps(out), flush=True)
     qd.shutdown(info)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(args, info, np, **arrays):
+    """--dump-outputs: rank 0's arrays of the last timed step, float64, DIR/<name>.npy (every config stays far below the 64 MiB cap)."""
+    if not args.dump_outputs or info.rank != 0:
+        return
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
 
 
 def base_line(args, cfg, info, value, tmax, scaling, metric="ADMM iterations/sec"):
@@ -286,6 +317,9 @@ def run_dense(args, cfg, info, device, qps, qd, np, sync, problem=None):
         iters_done += si["iterations"]; refactors += si["numRefactor"]; t_refactor += si["tRefactor"]; last = si
     sync(); qd.barrier(info)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        z, y = prob.dual()
+        dump_outputs(args, info, np, x=x, z=z, y=y)
     ktimes = prob.kernel_times()   # HIP-event times accumulated over the timed steps (reset by set_profiling)
     prob.set_profiling(0)
     value, tmax = qd.gather_timings(info, elapsed, iters_done)
@@ -379,6 +413,7 @@ def side_configs(args, info, device, qps, qd, np, sync):
             sa = argparse.Namespace(**vars(args))
             sa.config, sa.steps, sa.warmup, sa.iters = name, steps, 1, {"c3": 100, "c4": 100}.get(name, 500)
             sa.no_cpu_baseline = sa.no_time_to_eps = True
+            sa.dump_outputs = None           # --dump-outputs holds the headline's step only
             cfg = CONFIGS[name]
             if name == "c5":
                 o = run_dense(sa, cfg, info, device, qps, qd, np, sync, problem=KEEP.pop("c2_problem", None))
@@ -430,6 +465,7 @@ def run_sparse(args, cfg, info, device, qps, qd, np, sync):
         x = np.zeros(n); si = {}
         solver.solve(x, numIterations=args.iters, ϵAbs=0.0, ϵRel=0.0, info=si)
         cg["n"] += si["cgIterations"]
+        return x
     run()
     for _ in range(args.warmup):
         run()
@@ -438,9 +474,12 @@ def run_sparse(args, cfg, info, device, qps, qd, np, sync):
     qd.barrier(info); sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        x = run()
     sync(); qd.barrier(info)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        z, y = solver.dual()
+        dump_outputs(args, info, np, x=x, z=z, y=y)
     ktimes = solver.kernel_times()
     solver.set_profiling(0)
     value, tmax = qd.gather_timings(info, elapsed, args.iters * args.steps)
@@ -500,9 +539,12 @@ def run_batch(args, cfg, info, device, qps, qd, np, sync):
     t0 = time.perf_counter()
     infos = None
     for _ in range(args.steps):
-        _, _, infos = run()
+        X, _, infos = run()
     sync(); qd.barrier(info)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        Z, Y = solver.dual()
+        dump_outputs(args, info, np, x=X, z=Z, y=Y)
     ktimes = batch_kernel_times(solver)
     set_batch_profiling(solver, 0)
     units = (end - begin) * args.iters * args.steps

@@ -1,14 +1,23 @@
+# End-of-round refresh on a GPU machine: GPU suite, smoke, the --full bench line of c2 / c3 / c4 / c5, a kernel trace of the default --full command and
+# the HBM traffic of the headline's loop kernels (two separate PMC passes, never combined with other trace domains).  Stops at the first failing step.
+# Usage: bash tests/tools/final_refresh.sh <output dir>
 set -o pipefail
-R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out/final
-timeout -k 10 900 python -m pytest tests -m gpu -q > gpurun_out/final/pytest_gpu.log 2>&1; tail -2 gpurun_out/final/pytest_gpu.log
-timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/final/smoke.log 2>&1; tail -1 gpurun_out/final/smoke.log
-timeout -k 10 300 python bench.py > gpurun_out/final/bench.log 2>&1; tail -1 gpurun_out/final/bench.log > gpurun_out/final/bench.json; cut -c1-300 gpurun_out/final/bench.json
-for c in c3 c4 c5; do timeout -k 10 300 python bench.py --config $c > gpurun_out/final/bench_$c.log 2>&1; tail -1 gpurun_out/final/bench_$c.log > gpurun_out/final/bench_$c.json; cut -c1-200 gpurun_out/final/bench_$c.json; done
-cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/final/prof -o bench -- python3 $R/bench.py > $R/gpurun_out/final/prof.log 2>&1
-cd $R; f=$(find gpurun_out/final/prof -name "*kernel_stats.csv" | head -1); echo stats=$f; python tests/tools/print_stats.py $f 8
-# HBM traffic of the loop kernels: two separate PMC passes (never combined with other trace domains)
+R=$(cd "$(dirname "$0")/../.." && pwd); cd $R || exit 1
+mkdir -p "${1:?usage: final_refresh.sh <output dir>}" && O=$(cd "$1" && pwd) || exit 1
+step() { # log name, seconds, command...
+  n=$1; s=$2; shift 2
+  timeout -k 10 $s "$@" > $O/$n.log 2>&1 || { echo "$n failed ($?)"; tail -5 $O/$n.log; exit 1; }
+}
+step pytest_gpu 900 python -m pytest tests -m gpu -q; tail -2 $O/pytest_gpu.log
+step smoke 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"; tail -1 $O/smoke.log
+for c in c2 c3 c4 c5; do
+  step bench_$c 600 python bench.py --full --config $c; tail -1 $O/bench_$c.log > $O/bench_$c.json; cut -c1-300 $O/bench_$c.json
+done
+cd /tmp && export TMPDIR=/tmp
+step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --full
+cd $R; f=$(find $O/prof -name "*kernel_stats.csv" | head -1); echo stats=$f; python tests/tools/print_stats.py $f 8
 cd /tmp
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/final/pmc_f -o f -- python3 $R/bench.py --no-cpu-baseline --no-time-to-eps --steps 4 > $R/gpurun_out/final/pmc_f.log 2>&1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/final/pmc_w -o w -- python3 $R/bench.py --no-cpu-baseline --no-time-to-eps --steps 4 > $R/gpurun_out/final/pmc_w.log 2>&1
-cd $R; ff=$(find gpurun_out/final/pmc_f -name "*counter_collection.csv" | head -1); fw=$(find gpurun_out/final/pmc_w -name "*counter_collection.csv" | head -1)
-python tests/tools/pmc_summary.py $ff $fw gpurun_out/final/pmc_traffic.json > gpurun_out/final/pmc_traffic.txt 2>&1; sed -n 1,6p gpurun_out/final/pmc_traffic.txt
+step pmc_f 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -o f -- python3 $R/bench.py --steps 4
+step pmc_w 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -o w -- python3 $R/bench.py --steps 4
+cd $R; ff=$(find $O/pmc_f -name "*counter_collection.csv" | head -1); fw=$(find $O/pmc_w -name "*counter_collection.csv" | head -1)
+python tests/tools/pmc_summary.py $ff $fw $O/pmc_traffic.json > $O/pmc_traffic.txt 2>&1; sed -n 1,6p $O/pmc_traffic.txt

@@ -4,10 +4,10 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; cd $R; TAG=${1:-r02}; shift; CFGS=${@:-c2 c5 c3 c4 c1}
 O=gpurun_out/$TAG; mkdir -p $O
 for c in $CFGS; do
-  timeout -k 10 400 python bench.py --config $c > $O/bench_$c.log 2>&1 && tail -1 $O/bench_$c.log > $O/bench_$c.json && cut -c1-260 $O/bench_$c.json || { echo "bench $c FAILED"; tail -5 $O/bench_$c.log; }
+  timeout -k 10 400 python bench.py --full --config $c > $O/bench_$c.log 2>&1 && tail -1 $O/bench_$c.log > $O/bench_$c.json && cut -c1-260 $O/bench_$c.json || { echo "bench $c FAILED"; tail -5 $O/bench_$c.log; }
 done
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o bench -- python3 $R/bench.py --no-cpu-baseline > $R/$O/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o bench -- python3 $R/bench.py --full --no-cpu-baseline > $R/$O/prof.log 2>&1
 cd $R; f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_c2_kernel_stats.csv && python tests/tools/print_stats.py $f 10
 for c in $CFGS; do
   [ $c = c1 ] && continue

@@ -6,7 +6,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; cd $R; PART=${1:-bench}; TAG=${2:-r03z}; O=gpurun_out/$TAG; mkdir -p $O
 run_bench() { # name, args...
   n=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $O/bench_$n.log 2>&1 && tail -1 $O/bench_$n.log > $O/bench_$n.json && python - <<PY
+  timeout -k 10 400 python bench.py --full "$@" > $O/bench_$n.log 2>&1 && tail -1 $O/bench_$n.log > $O/bench_$n.json && python - <<PY
 import json; d=json.load(open("$O/bench_$n.json")); p=d.get("parity") or {}
 print("$n", d["value"], d["unit"], "roofline", (d.get("roofline") or {}).get("frac"), "parity", p.get("ok"), p.get("max_rel_dev_x"), "side" if "side_configs" in d else "")
 PY
