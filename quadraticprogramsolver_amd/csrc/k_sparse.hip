@@ -858,18 +858,8 @@ template <typename T> struct SparseSolver : SolverBase {
         M.nblocks = (int)rbv.size() - 1;
         M.rb = upload_array(rbv);
     }
-    void upload_vec(const double* h, T* d, int64_t count) {
-        if (count <= 0) return;
-        HIPC(hipMemcpyAsync(stage, h, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, st));
-        convert_copy<T>(st, stage, d, count);
-        HIPC(hipStreamSynchronize(st));
-    }
-    void download_vec(const T* d, double* h, int64_t count) {
-        if (count <= 0) return;
-        convert_back<T>(st, d, stage, count);
-        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
+    void upload_vec(const double* h, T* d, int64_t count) { HIPC(upload_staged<T>(st, stage, h, d, count)); }
+    void download_vec(const T* d, double* h, int64_t count) { HIPC(download_staged<T>(st, stage, d, h, count)); }
     // ItrSolCgInit (LinearSystemSolvers.jl:110-122): mAA = mA' * mA, mPI = mP + sigma I, mL = mPI + rho * mAA, formed on the host ONCE per handle as three value
     // arrays on the frozen pattern of mL (spmv_layout.cpp: reduced_matrix); returns whether the handle has it.  forced = an explicit QPS_LINSYS_CG_EXPLICIT request;
     // otherwise the matrix is only formed when it pays -- A'A cheap to form (sum of squared row lengths) and mL no larger than 1.5 x the entries the matrix-free

@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "batch_schedule.h"
+#include "dense_chol.h"
 #include "qps_internal.h"
 #include "spmv_layout.h"
 #include "qps_kernels.h"
@@ -99,15 +100,6 @@ ProfLaunchScope::~ProfLaunchScope() {
 namespace {
 
 thread_local std::string g_last_error;
-
-int pick_nb(int requested, int NP, bool cover = false) {
-    // default: one inverted block over the whole factor while the fused forward+backward sweep covers NP (`cover`), else 4096
-    int nb = requested > 0 ? requested : (cover ? 32768 : 4096);
-    int p = 64; while (p * 2 <= nb) p *= 2;   // power-of-two multiple of 64
-    nb = p;
-    while (nb > 64 && nb / 2 >= NP) nb /= 2;
-    return nb;
-}
 
 // =================================================================================================================
 // Dense problem, Cholesky path
@@ -226,18 +218,8 @@ template <typename T> struct DenseSolver : SolverBase {
     }
 
     // host double array -> device T vector (zero padded allocation is preserved beyond `count`)
-    void upload_vec(const double* h, T* d, int64_t count) {
-        if (count <= 0) return;
-        HIPC(hipMemcpyAsync(stage, h, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, st));
-        convert_copy<T>(st, stage, d, count);
-        HIPC(hipStreamSynchronize(st));
-    }
-    void download_vec(const T* d, double* h, int64_t count) {
-        if (count <= 0) return;
-        convert_back<T>(st, d, stage, count);
-        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
+    void upload_vec(const double* h, T* d, int64_t count) { HIPC(upload_staged<T>(st, stage, h, d, count)); }
+    void download_vec(const T* d, double* h, int64_t count) { HIPC(download_staged<T>(st, stage, d, h, count)); }
     // column-major host matrix -> row-major device T (streamed through a bounded staging buffer, column panels)
     void upload_matrix(const double* h, int64_t ldh, int rows, int cols, T* d, int64_t ldd) {
         if (rows <= 0 || cols <= 0) return;
@@ -262,28 +244,18 @@ template <typename T> struct DenseSolver : SolverBase {
         HIPC(hipFree(buf));
     }
 
+    DenseChol<T> chol() const { return {st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail}; }
     // LinSysSolInit: LinearSystemSolvers.jl:110-122 (mAA, mPI, mL) + factorisation (ProxQP.jl:196)
     void factorize(double rho, double sigma, bool rebuild_all) {
-        if (rebuild_all || !have_AA) {
-            make_PI<T>(st, (int)n, NP, P, (T)sigma, PI);                                             // :113
-            if (MP > 0) gemm<T>(st, NP, NP, MP, T(1), A, NP, false, A, NP, false, T(0), AA, NP, true); // :112 mAA = mA' mA
-            else HIPC(hipMemsetAsync(AA, 0, sizeof(T) * (size_t)NP * NP, st));
-            have_AA = true;
-        }
-        assemble_M<T>(st, NP, PI, AA, (T)rho, M);                                                    // :114 / :128
-        cholesky<T>(st, NP, M, dinv, fail, 1, chol_scratch_fits(NP) ? S : nullptr);   // S is rebuilt right after: free as scratch
-        build_sweep_matrix<T>(st, NP, nb, M, dinv, S, tmp, 1, use_blocked());
+        const bool rebuild = rebuild_all || !have_AA;
+        const DenseChol<T> c = chol();
+        factor_valid = false;
+        c.form(sigma, rho, rebuild, rebuild);                                                      // :112-114 / :128
+        have_AA = true;
+        c.factor(nb, 1, use_blocked());
+        char ctx[128]; snprintf(ctx, sizeof ctx, "rho=%g, sigma=%g; factorisation #%d of this handle", rho, sigma, ++num_factorizations);
         int f = 0;
-        HIPC(hipMemcpyAsync(&f, fail, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        ++num_factorizations;
-        if (f != 0) {
-            factor_valid = false;
-            char b[256];
-            if (f < 0) snprintf(b, sizeof b, "Cholesky of P + sigma I + rho A'A: the diagonal workgroup of a fused update launch gave up waiting for its two tiles (k_chol_update_diag; rho=%g, factorisation #%d of this handle)", rho, num_factorizations);
-            else snprintf(b, sizeof b, "Cholesky of P + sigma I + rho A'A broke down: non-positive pivot at column %d (rho=%g, sigma=%g; factorisation #%d of this handle)", f, rho, sigma, num_factorizations);
-            throw QpsError(QPS_ERR_FACTORIZATION, b);
-        }
+        c.check("P + sigma I + rho A'A", ctx, &f);
         factor_valid = true; fac_rho = rho; fac_sigma = sigma; fac_nb = nb; fac_premul = use_blocked();
     }
     // Did a blocked-sweep launch give up waiting (its workgroups were not co-resident: only another PROCESS running the same kernel on the card
@@ -302,51 +274,22 @@ template <typename T> struct DenseSolver : SolverBase {
         return true;
     }
 
-    int sweep_variant() const {
-        const int nblk = (NP + nb - 1) / nb;
-        if (nblk > 1 && fac_premul) return 5;
-        static const int sweep_mode = getenv("QPS_SWEEP_MODE") ? atoi(getenv("QPS_SWEEP_MODE")) : 2;
-        if (nblk == 1) return (sweep_mode == 2 && sweep_fused_supported<T>(NP)) ? 2 : 3;
-        return 1;
-    }
+    // the fused pass over one block first, then the single-launch blocked sweeps (5, at least two blocks), then the multi-launch sweeps
+    int sweep_variant() const { const int v = chol_sweep_variant<T>(NP, nb); return (fac_premul && v != 2) ? 5 : v; }
     // x~ = (L L')^{-1} tt via the blocked sweeps over S (tt is consumed)
     void sweeps() {
-        const int nblk = (NP + nb - 1) / nb;
-        static const int sweep_mode = getenv("QPS_SWEEP_MODE") ? atoi(getenv("QPS_SWEEP_MODE")) : 2;
-        if (nblk == 1 && sweep_mode == 2 && sweep_fused_supported<T>(NP)) {
-            // one inverted block: forward and backward sweep read the same entries -> one fused pass over the triangle
-            int G;
-            { ProfLaunchScope ps(prof, cat_sweep, sample_lvl(13)); G = sweep_fused<T>(st, S, NP, NP, tt, sw_part, NP); }
-            { ProfLaunchScope ps(prof, cat_xsum, sample_lvl(21)); colsum<T>(st, sw_part, NP, G, nullptr, T(0), nullptr, T(0), xx, NP); }
+        if (sweep_variant() != 5) {
+            chol().sweeps(nb, tt, yv, xx, sw_part, BatchStride(), {&prof, cat_sweep, sample_lvl(13), cat_xsum, sample_lvl(21), cat_fwd, cat_bwd, 2});
             return;
         }
-        if (fac_premul) {
-            // blocked substitution, one launch per sweep: n / nb dependent phases handed from workgroup to workgroup inside the launch
-            if (sweep_epoch >= 0xfffffff0u) {   // the granule tags are 32-bit launch counters: start over on a cleared buffer
-                HIPC(hipMemsetAsync(pub, 0, sizeof(unsigned long long) * (size_t)trsv_blocked_pub_words<T>(NP), st));
-                sweep_epoch = 0;
-            }
-            TrsvBlockedPair gate(device, st);   // never two of these persistent launches on the chip at once (k_trsv_blocked.hip, "Co-residency")
-            { ProfLaunchScope ps(prof, cat_fwd, sample_lvl(13)); trsv_blocked<T>(st, false, S, NP, NP, nb, tt, yv, pub, ++sweep_epoch, abort_dev); }
-            { ProfLaunchScope ps(prof, cat_bwd, sample_lvl(21)); trsv_blocked<T>(st, true, S, NP, NP, nb, yv, xx, pub, ++sweep_epoch, abort_dev); }
-            return;
+        // blocked substitution, one launch per sweep: n / nb dependent phases handed from workgroup to workgroup inside the launch
+        if (sweep_epoch >= 0xfffffff0u) {   // the granule tags are 32-bit launch counters: start over on a cleared buffer
+            HIPC(hipMemsetAsync(pub, 0, sizeof(unsigned long long) * (size_t)trsv_blocked_pub_words<T>(NP), st));
+            sweep_epoch = 0;
         }
-        {
-            ProfScope ps(prof, cat_fwd, 2);
-            for (int J = 0; J < nblk; ++J) {
-                const int r0 = J * nb, r1 = std::min(NP, r0 + nb);
-                gemv_rows<T>(st, S, NP, tt, yv, nullptr, T(1), T(0), r0, r1, r0, r1, 1);
-                if (r1 < NP) gemv_rows<T>(st, S, NP, yv, tt, tt, T(-1), T(1), r1, NP, r0, r1, 0);
-            }
-        }
-        {
-            ProfScope ps(prof, cat_bwd, 2);
-            for (int J = nblk - 1; J >= 0; --J) {
-                const int r0 = J * nb, r1 = std::min(NP, r0 + nb);
-                gemv_rows<T>(st, S, NP, yv, xx, nullptr, T(1), T(0), r0, r1, r0, r1, 2);
-                if (r0 > 0) gemv_rows<T>(st, S, NP, xx, yv, yv, T(-1), T(1), 0, r0, r0, r1, 0);
-            }
-        }
+        TrsvBlockedPair gate(device, st);   // never two of these persistent launches on the chip at once (k_trsv_blocked.hip, "Co-residency")
+        { ProfLaunchScope ps(prof, cat_fwd, sample_lvl(13)); trsv_blocked<T>(st, false, S, NP, NP, nb, tt, yv, pub, ++sweep_epoch, abort_dev); }
+        { ProfLaunchScope ps(prof, cat_bwd, sample_lvl(21)); trsv_blocked<T>(st, true, S, NP, NP, nb, yv, xx, pub, ++sweep_epoch, abort_dev); }
     }
     // LinSysSol! body: LinearSystemSolvers.jl:134-139
     void linear_solve(double rho, double sigma) {
@@ -380,7 +323,7 @@ template <typename T> struct DenseSolver : SolverBase {
         if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CHOLESKY)
             throw QpsError(QPS_ERR_UNSUPPORTED, "dense handles offer QPS_LINSYS_CHOLESKY only (qps_create_csc with dense_path = 0 for the CG and the sparse L D L' plugins)");
         const double t0 = now_s();
-        nb = pick_nb(p.trsvBlock, NP, sweep_fused_supported<T>(NP));
+        nb = pick_nb<T>(p.trsvBlock, NP);
         double rho = p.rho, sigma = p.sigma; const double alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         int convFlag = QPS_CONV_NUM_ITR;                                                            // :33
@@ -550,7 +493,7 @@ template <typename T> struct DenseSolver : SolverBase {
     void linsys_init(double rho, double sigma, int linsys, int nbreq) override {
         HIPC(hipSetDevice(device));
         if (linsys != QPS_LINSYS_AUTO && linsys != QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "dense handles support QPS_LINSYS_CHOLESKY only");
-        nb = pick_nb(nbreq, NP, sweep_fused_supported<T>(NP));
+        nb = pick_nb<T>(nbreq, NP);
         blocked_off = false;
         factorize(rho, sigma, true);
     }
@@ -601,7 +544,7 @@ struct BatchSolverBase {
 
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
     hipStream_t st = nullptr;
-    int NP = 0, MP = 0, nb = 0, slabs = 0, rpw = 0, part_tiles = 0, sw_slabs = 0;
+    int NP = 0, MP = 0, nb = 0, slabs = 0, rpw = 0, part_tiles = 0;
     T *A = nullptr, *P = nullptr, *q = nullptr, *l = nullptr, *u = nullptr, *PI = nullptr, *AA = nullptr, *M = nullptr, *S = nullptr,
       *tmp = nullptr, *dinv = nullptr;
     T *x = nullptr, *xp = nullptr, *xres = nullptr, *z = nullptr, *y = nullptr, *xx = nullptr, *tt = nullptr, *yv = nullptr, *part = nullptr,
@@ -637,7 +580,7 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
         int rpw1 = 0;
         const int64_t part_slabs = std::max<int64_t>(std::max<int64_t>(c * slabs, apass_plan<T>(NP, MP, &rpw1, 1)), std::max(part_tiles, 1));
         part = dalloc<T>(part_slabs * NP, st); part2 = dalloc<T>(c * slabs * NP, st); part_tmp = dalloc<T>((int64_t)std::max(part_tiles, 1) * NP, st);
-        sw_slabs = sweep_fused_slabs<T>(NP, count); sw_part = dalloc<T>(c * std::max(sw_slabs, 1) * NP, st);
+        const int sw_slabs = sweep_fused_slabs<T>(NP, count); sw_part = dalloc<T>(c * std::max(sw_slabs, 1) * NP, st);
         fail = dalloc<int>(count + 4, st); d_active = dalloc<int>(count + 4, st); d_rho = dalloc<double>(count + 4, st); d_rhorho = dalloc<double>(count + 4, st);
         scratch = dalloc<unsigned long long>(16 * c, st); res_dev = dalloc<double>(8 * c, st);
         HIPC(hipHostMalloc((void**)&res_host, 8 * c * sizeof(double)));
@@ -679,8 +622,8 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
     void get_dual(double* zh, double* yh) override {
         HIPC(hipSetDevice(device));
         for (int b = 0; b < count && m > 0; ++b) {
-            if (zh) { convert_back<T>(st, z + (int64_t)b * MP, stage, m); HIPC(hipMemcpyAsync(zh + (int64_t)b * m, stage, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
-            if (yh) { convert_back<T>(st, y + (int64_t)b * MP, stage, m); HIPC(hipMemcpyAsync(yh + (int64_t)b * m, stage, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
+            if (zh) HIPC(download_staged<T>(st, stage, z + (int64_t)b * MP, zh + (int64_t)b * m, m));
+            if (yh) HIPC(download_staged<T>(st, stage, y + (int64_t)b * MP, yh + (int64_t)b * m, m));
         }
     }
     void load_problem(int b, const double* Ph, const double* Ah, const double* qh, const double* lh, const double* uh) {
@@ -688,39 +631,9 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
         put_matrix(Ah, (int)m, (int)n, A + (int64_t)b * MP * NP);
         put_vec(qh, q + (int64_t)b * NP, n); put_vec(lh, l + (int64_t)b * MP, m); put_vec(uh, u + (int64_t)b * MP, m);
     }
-    // LinearSystemSolvers.jl:112-114 / :127-129 for QP b (no host synchronisation; fail[b] is read later)
-    void factorize_one(int b, double rho, double sigma, bool rebuild) {
-        const int64_t nn = (int64_t)NP * NP;
-        T *Pb = P + b * nn, *Ab = A + (int64_t)b * MP * NP, *PIb = PI + b * nn, *AAb = AA + b * nn, *Mb = M + b * nn, *Sb = S + b * nn;
-        if (rebuild) {
-            make_PI<T>(st, (int)n, NP, Pb, (T)sigma, PIb);
-            gemm<T>(st, NP, NP, MP, T(1), Ab, NP, false, Ab, NP, false, T(0), AAb, NP, true);
-        }
-        assemble_M<T>(st, NP, PIb, AAb, (T)rho, Mb);
-        T* dinvb = dinv + (int64_t)b * (NP / 64) * 4096;
-        cholesky<T>(st, NP, Mb, dinvb, fail + b, 1, chol_scratch_fits(NP) ? Sb : nullptr);
-        build_sweep_matrix<T>(st, NP, nb, Mb, dinvb, Sb, tmp + b * nn);
-    }
-    // all QPs at once (same rho): every launch of the panel chain carries the whole batch
-    void factorize_all(double rho, double sigma, bool rebuild, const double* rho_arr = nullptr) {
-        const int64_t nn = (int64_t)NP * NP;
-        if (rebuild) {
-            make_PI<T>(st, (int)n, NP, P, (T)sigma, PI, count);
-            gemm<T>(st, NP, NP, MP, T(1), A, NP, false, A, NP, false, T(0), AA, NP, true, count, (int64_t)MP * NP, (int64_t)MP * NP, nn);
-        }
-        assemble_M<T>(st, NP, PI, AA, (T)rho, M, count, rho_arr);
-        cholesky<T>(st, NP, M, dinv, fail, count, chol_scratch_fits(NP) ? S : nullptr);
-        build_sweep_matrix<T>(st, NP, nb, M, dinv, S, tmp, count);
-    }
-    void check_fail(const std::vector<int>& which) {
-        if (which.empty()) return;
-        HIPC(hipMemcpyAsync(h_int, fail, sizeof(int) * count, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        for (int b : which) if (h_int[b] != 0) {
-            char buf[256]; snprintf(buf, sizeof buf, "QP %d of the batch: Cholesky of P + sigma I + rho A'A broke down at column %d", b, h_int[b]);
-            throw QpsError(QPS_ERR_FACTORIZATION, buf);
-        }
-    }
+    // LinearSystemSolvers.jl:112-114 / :127-129: chol() covers the whole batch (every launch of the panel chain carries all QPs), chol().at(b) QP b alone;
+    // no host synchronisation until its check() reads the fail words
+    DenseChol<T> chol() const { return {st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail}; }
     void push_state(const std::vector<double>& rho, const std::vector<double>& rhorho, const std::vector<int>& active) {
         for (int b = 0; b < count; ++b) { h_dbl[b] = rho[b]; h_dbl[count + 4 + b] = rhorho[b]; h_int[b] = active[b]; }
         HIPC(hipMemcpyAsync(d_rho, h_dbl, sizeof(double) * count, hipMemcpyHostToDevice, st));
@@ -733,7 +646,9 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
         HIPC(hipSetDevice(device));
         const double t0 = now_s();
         if (slabs <= 0) throw QpsError(QPS_ERR_UNSUPPORTED, "batched path needs m >= 1 and n within the fused-pass limit");
-        nb = pick_nb(p.trsvBlock, NP, sweep_fused_supported<T>(NP));
+        nb = pick_nb<T>(p.trsvBlock, NP);
+        const DenseChol<T> ch = chol();
+        const char* what = "P + sigma I + rho A'A";
         const double sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;
         std::vector<double> rho(count, p.rho), rhorho(count, p.rho), resP(count, NAN), resD(count, NAN), tref(count, 0.0);
@@ -745,9 +660,9 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
         std::vector<int> todo;
         for (int b = 0; b < count; ++b)                                                             // SolveQuadraticProgram.jl:36
             if (rebuild || fac_rho[b] != p.rho || fac_nb != nb) todo.push_back(b);
-        if ((int)todo.size() == count) factorize_all(p.rho, sigma, rebuild);
-        else for (int b : todo) factorize_one(b, p.rho, sigma, rebuild);
-        check_fail(todo);
+        if ((int)todo.size() == count) { ch.form(sigma, p.rho, rebuild, rebuild, count); ch.factor(nb, count); }
+        else for (int b : todo) { ch.at(b).form(sigma, p.rho, rebuild, rebuild); ch.at(b).factor(nb); }
+        ch.check(what, "", h_int, count, &todo);
         have_AA = true; fac_sigma = sigma; fac_nb = nb;
         for (int b : todo) fac_rho[b] = p.rho;
         for (int b = 0; b < count; ++b) put_vec(xh + (int64_t)b * n, x + (int64_t)b * NP, n);
@@ -793,9 +708,9 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
                 if (!changed.empty()) {
                     const double ta = now_s();
                     const bool together = (int)changed.size() * 2 >= count;
-                    if (together) { push_state(rho, rhorho, active); factorize_all(0.0, sigma, false, d_rho); for (int b = 0; b < count; ++b) fac_rho[b] = rho[b]; }
-                    else for (int b : changed) { factorize_one(b, rho[b], sigma, false); fac_rho[b] = rho[b]; }
-                    if (together) check_fail(all); else check_fail(changed);
+                    if (together) { push_state(rho, rhorho, active); ch.form(sigma, 0.0, false, false, count, d_rho); ch.factor(nb, count); for (int b = 0; b < count; ++b) fac_rho[b] = rho[b]; }
+                    else for (int b : changed) { ch.at(b).form(sigma, rho[b], false, false); ch.at(b).factor(nb); fac_rho[b] = rho[b]; }
+                    ch.check(what, "", h_int, count, together ? &all : &changed);
                     const double dt = (now_s() - ta) / changed.size();
                     for (int b : changed) tref[b] += dt;
                 }
@@ -814,11 +729,12 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
                 const bool together = (int)changed.size() * 2 >= count;   // most QPs switch at the same check: one batched refactor
                 if (together) {
                     push_state(rho, rhorho, active);                      // d_rho must hold the new values before assembly
-                    factorize_all(0.0, sigma, false, d_rho);
+                    ch.form(sigma, 0.0, false, false, count, d_rho);
+                    ch.factor(nb, count);
                     for (int b = 0; b < count; ++b) fac_rho[b] = rho[b];
                 }
                 for (int b : changed) {
-                    if (!together) { factorize_one(b, rho[b], sigma, false); fac_rho[b] = rho[b]; }
+                    if (!together) { ch.at(b).form(sigma, rho[b], false, false); ch.at(b).factor(nb); fac_rho[b] = rho[b]; }
                     if (rhs_slabs > 0) {   // slabs of A'(rho z - y) depend on rho: rebuild them for this QP (slab 0 = the sum, rest 0)
                         T* pb_ = part + (int64_t)b * slabs * NP;
                         gemv_cols_partial<T>(st, A + (int64_t)b * MP * NP, NP, z + (int64_t)b * MP, y + (int64_t)b * MP, (T)rho[b], T(-1), part_tmp, NP, MP, NP);
@@ -826,30 +742,14 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
                         if (slabs > 1) HIPC(hipMemsetAsync(pb_ + NP, 0, sizeof(T) * (size_t)(slabs - 1) * NP, st));
                     }
                 }
-                if (together) check_fail(all); else check_fail(changed);
+                ch.check(what, "", h_int, count, together ? &all : &changed);
                 push_state(rho, rhorho, active);
                 const double dt = (now_s() - ta) / changed.size();
                 for (int b : changed) tref[b] += dt;
             }
             const bool check = (ii % p.numItrConv == 0);
             colsum<T>(st, part, NP, rhs_slabs, x, (T)sigma, q, T(-1), tt, NP, bsC);                  // LinearSystemSolvers.jl:136
-            if (nblk == 1 && sweep_fused_supported<T>(NP)) {                                       // both sweeps in one pass
-                BatchStride bsW = bsS; bsW.vout = (int64_t)sw_slabs * NP;
-                { ProfLaunchScope ps(prof, cat_sweep, (prof.level == 1 && ii % 50 == 13) ? 1 : 2); sweep_fused<T>(st, S, NP, NP, tt, sw_part, NP, bsW); }
-                BatchStride bsX = bsS; bsX.mat = (int64_t)sw_slabs * NP;
-                colsum<T>(st, sw_part, NP, sw_slabs, nullptr, T(0), nullptr, T(0), xx, NP, bsX);
-            } else
-            for (int J = 0; J < nblk; ++J) {                                                        // forward sweep
-                const int r0 = J * nb, r1 = std::min(NP, r0 + nb);
-                gemv_rows<T>(st, S, NP, tt, yv, nullptr, T(1), T(0), r0, r1, r0, r1, 1, bsS);
-                if (r1 < NP) gemv_rows<T>(st, S, NP, yv, tt, tt, T(-1), T(1), r1, NP, r0, r1, 0, bsS);
-            }
-            if (!(nblk == 1 && sweep_fused_supported<T>(NP)))
-            for (int J = nblk - 1; J >= 0; --J) {                                                   // backward sweep
-                const int r0 = J * nb, r1 = std::min(NP, r0 + nb);
-                gemv_rows<T>(st, S, NP, yv, xx, nullptr, T(1), T(0), r0, r1, r0, r1, 2, bsS);
-                if (r0 > 0) gemv_rows<T>(st, S, NP, xx, yv, yv, T(-1), T(1), 0, r0, r0, r1, 0, bsS);
-            }
+            ch.sweeps(nb, tt, yv, xx, sw_part, bsS, {&prof, cat_sweep, (prof.level == 1 && ii % 50 == 13) ? 1 : 2});   // :137
             if (check) HIPC(hipMemsetAsync(scratch, 0, 16 * sizeof(unsigned long long) * count, st));
             {
                 ProfLaunchScope ps(prof, cat_pass, (prof.level == 1 && !check && ii % 50 == 38) ? 1 : (check ? 3 : 2));   // level 1: one plain launch in 50
@@ -891,16 +791,14 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
                 polish_dense<T>(st, n, m, NP, MP, P + (int64_t)b * NP * NP, A + (int64_t)b * MP * NP, q + (int64_t)b * NP, l + (int64_t)b * MP,
                                 u + (int64_t)b * MP, y + (int64_t)b * MP, xres + (int64_t)b * NP, part, p, &pol[b]);
         for (int b = 0; b < count; ++b) {
-            convert_back<T>(st, xres + (int64_t)b * NP, stage, n);
-            HIPC(hipMemcpyAsync(xh + (int64_t)b * n, stage, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
+            HIPC(download_staged<T>(st, stage, xres + (int64_t)b * NP, xh + (int64_t)b * n, n));
             if (infos) {
                 qps_info& in = infos[b];
                 in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
                 in.rhoFinal = rho[b]; in.rhoProposed = rhorho[b]; in.resPrim = resP[b]; in.resDual = resD[b];
                 in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref[b];   // wall time of the whole batch
                 in.polishFlag = pol[b].flag; in.polishIterations = pol[b].minresIterations; in.tPolish = pol[b].seconds;
-                in.trsvBlock = nb; in.sweepVariant = (nblk == 1 && sweep_fused_supported<T>(NP)) ? 2 : (nblk == 1 ? 3 : 1);
+                in.trsvBlock = nb; in.sweepVariant = chol_sweep_variant<T>(NP, nb);
                 in.sweepGaveUp = 0; in.cgExplicit = 0;
             }
         }

@@ -142,6 +142,21 @@ void admm_small_read(const void* host_copy, int* last_it, int* convFlag, int* ne
 template <typename T> void fill(hipStream_t st, T* p, int64_t n, T v);
 template <typename T> void convert_copy(hipStream_t st, const double* src, T* dst, int64_t n);   // dst[i] = (T)src[i]
 template <typename T> void convert_back(hipStream_t st, const T* src, double* dst, int64_t n);   // dst[i] = (double)src[i]
+// n host doubles -> device T (or back) through the device staging buffer `stage` (n doubles), then the stream is synchronised: the host array may
+// be reused or read at once.  n <= 0 does nothing.
+template <typename T> inline hipError_t upload_staged(hipStream_t st, double* stage, const double* h, T* d, int64_t n) {
+    if (n <= 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(stage, h, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    convert_copy<T>(st, stage, d, n);
+    return hipStreamSynchronize(st);
+}
+template <typename T> inline hipError_t download_staged(hipStream_t st, double* stage, const T* d, double* h, int64_t n) {
+    if (n <= 0) return hipSuccess;
+    convert_back<T>(st, d, stage, n);
+    const hipError_t e = hipMemcpyAsync(h, stage, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
 
 // ---- setup kernels (k_setup.hip) -----------------------------------------------------------------------------
 // dst (row-major rows x NPc, zero padded to rowsP x NPc) = transpose-of-column-major src (rows x cols, ld lds) as T

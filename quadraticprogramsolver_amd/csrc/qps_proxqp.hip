@@ -12,6 +12,7 @@
 // device by the range-space method: x = -P^{-1}(q + A'y), (A P^{-1} A') y = -(b + A P^{-1} q).
 #include <algorithm>
 
+#include "dense_chol.h"
 #include "qps_internal.h"
 #include "qps_kernels.h"
 #include "qps_proxqp.h"
@@ -70,18 +71,8 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
         for (void* p_ : ptrs) if (p_) (void)hipFree(p_);
         if (res.st) recycle_resources(device, res);
     }
-    void put_vec(const double* h, T* d, int64_t c) {
-        if (c <= 0) return;
-        HIPC(hipMemcpyAsync(stage, h, sizeof(double) * (size_t)c, hipMemcpyHostToDevice, st));
-        convert_copy<T>(st, stage, d, c);
-        HIPC(hipStreamSynchronize(st));
-    }
-    void get_vec(const T* d, double* h, int64_t c) {
-        if (c <= 0) return;
-        convert_back<T>(st, d, stage, c);
-        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)c, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
+    void put_vec(const double* h, T* d, int64_t c) { HIPC(upload_staged<T>(st, stage, h, d, c)); }
+    void get_vec(const T* d, double* h, int64_t c) { HIPC(download_staged<T>(st, stage, d, h, c)); }
     void put_matrix(const double* h, int64_t ldh, int rows, int cols, T* d) {   // column-major host -> row-major device rows (ld NP)
         if (rows <= 0 || cols <= 0) return;
         HIPC(hipMemcpy2DAsync(stage, sizeof(double) * (size_t)rows, h, sizeof(double) * (size_t)ldh, sizeof(double) * (size_t)rows, (size_t)cols, hipMemcpyHostToDevice, st));
@@ -95,46 +86,17 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
         put_matrix(Ch, ldc, (int)mi, (int)n, G + (int64_t)me * NP);
         put_vec(qh, q, n); put_vec(bh, g, me); put_vec(dh, g + me, mi);
     }
-    void check_fail(const char* what) {
-        int f = 0;
-        HIPC(hipMemcpyAsync(&f, fail, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        if (f != 0) { char b_[256]; snprintf(b_, sizeof b_, "Cholesky of %s broke down: non-positive pivot at column %d", what, f); throw QpsError(QPS_ERR_FACTORIZATION, b_); }
-    }
-    // tt -> xx = (L L')^{-1} tt with the sweep matrix Sm (NPm x NPm)
-    void sweeps(const T* Sm, int NPm, int nbm, T* rhs, T* out, T* work) {
-        const int nblk = (NPm + nbm - 1) / nbm;
-        if (nblk == 1 && sweep_fused_supported<T>(NPm)) {
-            const int Gs = sweep_fused<T>(st, Sm, NPm, NPm, rhs, sw_part, NPm);
-            colsum<T>(st, sw_part, NPm, Gs, nullptr, T(0), nullptr, T(0), out, NPm);
-            return;
-        }
-        for (int J = 0; J < nblk; ++J) {
-            const int r0 = J * nbm, r1 = std::min(NPm, r0 + nbm);
-            gemv_rows<T>(st, Sm, NPm, rhs, work, nullptr, T(1), T(0), r0, r1, r0, r1, 1);
-            if (r1 < NPm) gemv_rows<T>(st, Sm, NPm, work, rhs, rhs, T(-1), T(1), r1, NPm, r0, r1, 0);
-        }
-        for (int J = nblk - 1; J >= 0; --J) {
-            const int r0 = J * nbm, r1 = std::min(NPm, r0 + nbm);
-            gemv_rows<T>(st, Sm, NPm, work, out, nullptr, T(1), T(0), r0, r1, r0, r1, 2);
-            if (r0 > 0) gemv_rows<T>(st, Sm, NPm, out, work, work, T(-1), T(1), 0, r0, r0, r1, 0);
-        }
-    }
-    // one inverted block over the whole factor while the fused forward+backward sweep covers it (as DenseSolver does), else 4096-blocks
-    int pick(int NPm) { const int cap = sweep_fused_supported<T>(NPm) ? 32768 : 4096; int p = 64; while (p < NPm && p < cap) p *= 2; return p; }
+    DenseChol<T> chol() const { return {st, (int)n, NP, MP, P, G, PI, KK, M, S, tmp, dinv, fail}; }
 
     // UpdateDecomposition! (ProxQP.jl:193-199): M = P + rho K + sigma I, Cholesky, sweep matrix
     void update_decomposition(double rho, double sigma) {
-        if (!have_K) {
-            gemm<T>(st, NP, NP, MP, T(1), G, NP, false, G, NP, false, T(0), KK, NP, true);          // mK = A'A + C'C (:42-46)
-            have_K = true;
-        }
-        make_PI<T>(st, (int)n, NP, P, (T)sigma, PI);
-        assemble_M<T>(st, NP, PI, KK, (T)rho, M);                                                   // :178-180
-        cholesky<T>(st, NP, M, dinv, fail, 1, chol_scratch_fits(NP) ? S : nullptr);                 // :196
-        nb = pick(NP);
-        build_sweep_matrix<T>(st, NP, nb, M, dinv, S, tmp);
-        check_fail("P + rho (A'A + C'C) + sigma I");
+        const DenseChol<T> c = chol();
+        c.form(sigma, rho, true, !have_K);                                                          // mK = A'A + C'C (:42-46) once, :178-180
+        have_K = true;
+        nb = pick_nb<T>(0, NP);
+        c.factor(nb);                                                                               // :196
+        int f = 0;
+        c.check("P + rho (A'A + C'C) + sigma I", "", &f);
     }
 
     void set_state(const double* xh, const double* yh, const double* zh, const double* sh) override {
@@ -154,12 +116,13 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
     // ProxQP.jl:73-93 on the device (range-space method; P is SPD as the reference requires, A needs full row rank)
     void init_kkt() override {
         HIPC(hipSetDevice(device));
-        const int nbP = pick(NP);
+        const DenseChol<T> cP = chol();
+        const int nbP = pick_nb<T>(0, NP);
+        int f = 0;
         make_PI<T>(st, (int)n, NP, P, T(0), PI);                     // P with identity on the padding
         HIPC(hipMemcpyAsync(M, PI, sizeof(T) * (size_t)NP * NP, hipMemcpyDeviceToDevice, st));
-        cholesky<T>(st, NP, M, dinv, fail, 1, chol_scratch_fits(NP) ? S : nullptr);
-        build_sweep_matrix<T>(st, NP, nbP, M, dinv, S, tmp);         // S: sweep matrix of P
-        check_fail("P (KKT initialisation)");
+        cP.factor(nbP);                                              // S: sweep matrix of P
+        cP.check("P (KKT initialisation)", "", &f);
         HIPC(hipMemsetAsync(dual, 0, sizeof(T) * MP, st));
         if (me > 0) {
             if (nbP < NP) throw QpsError(QPS_ERR_UNSUPPORTED, "KKT initialisation of the dense solver needs n <= 16384 fp64 / 32768 fp32 (pass an explicit state, or CSC inputs for the sparse solver)");
@@ -173,17 +136,17 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
             gemm<T>(st, MEP, MEP, NP, T(1), B, MEP, false, B, MEP, false, T(0), Sch, MEP, false);
             T* SchPI = M;                                            // Schur + identity on its padding
             make_PI<T>(st, (int)me, MEP, Sch, T(0), SchPI);
-            T* dinv2 = dinv; T* S2 = Wl;                             // Wl no longer needed after the two GEMMs
-            cholesky<T>(st, MEP, SchPI, dinv2, fail, 1, chol_scratch_fits(MEP) ? S2 : nullptr);
-            const int nb2 = pick(MEP);
-            build_sweep_matrix<T>(st, MEP, nb2, SchPI, dinv2, S2, B);
-            check_fail("A P^{-1} A' (KKT initialisation: A must have full row rank)");
+            DenseChol<T> cS = cP;                                    // the Schur factor: order MEP, its sweep matrix in Wl (no longer needed
+            cS.NP = MEP; cS.M = SchPI; cS.S = Wl; cS.tmp = B;         // after the two GEMMs), B as scratch, dinv and fail shared with P's
+            const int nb2 = pick_nb<T>(0, MEP);
+            cS.factor(nb2);
+            cS.check("A P^{-1} A' (KKT initialisation: A must have full row rank)", "", &f);
             // u = P^{-1} q ; t = b + A u ; y = -Schur^{-1} t
             HIPC(hipMemcpyAsync(tt, q, sizeof(T) * NP, hipMemcpyDeviceToDevice, st));
-            sweeps(S, NP, nbP, tt, xx, yv);
+            cP.sweeps(nbP, tt, yv, xx, sw_part);
             gemv_rows<T>(st, Aonly, NP, xx, w, g, T(1), T(1), 0, MEP, 0, NP, 0);                    // w = A u + b  (padding rows: 0 + g? g holds d there)
             HIPC(hipMemsetAsync(w + me, 0, sizeof(T) * (size_t)(MEP - me), st));
-            sweeps(S2, MEP, nb2, w, de, di);                                                        // de = Schur^{-1} t
+            cS.sweeps(nb2, w, di, de, sw_part);                                                     // de = Schur^{-1} t
             hipLaunchKernelGGL((k_pq_scale_add<T>), g1((int)me), dim3(256), 0, st, (int)me, T(-1), de, T(0), (const T*)nullptr, dual);   // y
         }
         // x = -P^{-1}(q + A'y)
@@ -191,7 +154,7 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
         if (me > 0) HIPC(hipMemcpyAsync(de, dual, sizeof(T) * (size_t)me, hipMemcpyDeviceToDevice, st));
         const int tiles = gemv_cols_partial<T>(st, Aonly, NP, de, nullptr, T(1), T(0), part, NP, MEP, NP);
         colsum<T>(st, part, NP, tiles, q, T(1), nullptr, T(0), tt, NP);
-        sweeps(S, NP, nbP, tt, xx, yv);
+        cP.sweeps(nbP, tt, yv, xx, sw_part);
         hipLaunchKernelGGL((k_pq_scale_add<T>), g1(NP), dim3(256), 0, st, NP, T(-1), xx, T(0), (const T*)nullptr, x);
         // s = max(d - C x, 0), z = 0                                                               (:88-89)
         gemv_rows<T>(st, G, NP, x, v, nullptr, T(1), T(0), 0, MP, 0, NP, 0);
@@ -216,7 +179,7 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
                 slabs = gemv_cols_partial<T>(st, G, NP, w, nullptr, T(1), T(0), part, NP, MP, NP);        // G'w (:213,216)
             }
             colsum<T>(st, part, NP, slabs, x, (T)sigma, q, T(-1), tt, NP);                            // :211
-            sweeps(S, NP, nb, tt, x, yv);                                                           // :224 (no relaxation: x = M^{-1} r)
+            chol().sweeps(nb, tt, yv, x, sw_part);                                                  // :224 (no relaxation: x = M^{-1} r)
             if (fused && !check) {
                 slabs = apass_proxqp<T>(st, G, NP, NP, MP, (int)me, x, xx, slack, dual, g, (T)rho, part, NP);   // :227-249 + next :212-216
             } else {
