@@ -298,10 +298,9 @@ __global__ __launch_bounds__(256) void k_spanel(T* __restrict__ M, int64_t ld, i
 }
 
 template <typename T> struct DevVec {
-    T* p = nullptr; int64_t n = 0;
-    void alloc(int64_t count, hipStream_t st) { n = count; p = dalloc<T>(count, st); }
+    T* p = nullptr; int64_t n = 0; DeviceOwner own;
+    void alloc(int64_t count, hipStream_t st) { own.release(p); p = nullptr; n = count; p = own.dalloc<T>(count, st); }
     void upload(const std::vector<T>& h, StagedUploader& up) { alloc((int64_t)h.size(), up.st); if (!h.empty()) up.copy(p, h.data(), sizeof(T) * h.size()); }
-    ~DevVec() { if (p) (void)hipFree(p); }
 };
 
 int pick_lpr(int64_t nnz, int rows) {

@@ -761,7 +761,8 @@ struct Csr {
 };
 
 template <typename T> struct SparseSolver : SolverBase {
-    HandleResources res; std::unique_ptr<StagedUploader> up;   // `up` lives for the duration of the constructor only
+    // destroyed in reverse: what works on the stream (`ldl` below, `up`), the buffers, the stream lease, then the base's Profiler
+    StreamLease lease; DeviceOwner mem; std::unique_ptr<StagedUploader> up;   // `up` lives for the duration of the constructor only
     Csr A, At, P, PA;   // PA = [P; A] stacked, column-blocked only: P u and A u of the CG operator from ONE pass over u
     // ItrSolCgInit / ItrSolCg! (LinearSystemSolvers.jl:110-142): the explicit reduced matrix mL = mPI + rho mAA on a frozen pattern; ONE product per CG iteration
     Csr Lm; T *L_vP = nullptr, *L_vAA = nullptr, *L_dg = nullptr;
@@ -803,7 +804,7 @@ template <typename T> struct SparseSolver : SolverBase {
     // Column-blocked copy of M: the sliced form (k_spmv_sell) when the host builder produces one, else the task form (k_spmv_blk).  The layouts are
     // built by plain host code (spmv_layout.cpp, tested on the CPU against scipy); here they are only uploaded.
     template <typename V> V* upload_array(const std::vector<V>& v, int64_t min_count = 1) {
-        V* d = dalloc<V>(std::max<int64_t>((int64_t)v.size(), min_count), st);
+        V* d = mem.dalloc<V>(std::max<int64_t>((int64_t)v.size(), min_count), st);
         if (!v.empty()) up->copy(d, v.data(), sizeof(V) * v.size());
         return d;
     }
@@ -822,7 +823,7 @@ template <typename T> struct SparseSolver : SolverBase {
                 M.bci = upload_array(L.lci); M.bva = upload_array(L.lva);
                 M.sl_off = upload_array(L.sl_off); M.sl_perm = upload_array(L.perm); M.wg_ptr = upload_array(L.wg_ptr);
                 M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
-                M.partial = dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);
+                M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);
                 M.blocked = true; M.sell = true;
                 return;
             }
@@ -835,7 +836,7 @@ template <typename T> struct SparseSolver : SolverBase {
         M.brp = upload_array(L.brp); M.bci = upload_array(L.bci); M.bva = upload_array(L.bva);
         M.task_ptr = upload_array(L.task_ptr); M.tasks = reinterpret_cast<int4*>(upload_array(L.tasks));
         M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
-        M.partial = dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);    // + 64: the dump slots of lanes without a row
+        M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);    // + 64: the dump slots of lanes without a row
         M.blocked = true;
     }
     void upload_csr(Csr& M, const layout::CsrHost& H, bool with_src = false) {
@@ -888,8 +889,8 @@ template <typename T> struct SparseSolver : SolverBase {
         up.reset();
         HIPC(hipStreamSynchronize(st));
         if (dot_parts(Lm) + 64 > part_uc_cap) {                                                     // partials of dot(u, mL u): one per workgroup of the product's last launch
-            (void)hipFree(part_uc);
-            part_uc_cap = dot_parts(Lm) + 64; part_uc = dalloc<double>(part_uc_cap, st);
+            mem.release(part_uc); part_uc = nullptr;
+            part_uc_cap = dot_parts(Lm) + 64; part_uc = mem.dalloc<double>(part_uc_cap, st);
         }
         explicit_state = 1; L_valid = false;
         return true;
@@ -959,9 +960,8 @@ template <typename T> struct SparseSolver : SolverBase {
                  const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* qh, const double* lh, const double* uh, int base) {
         device = dev; n = n_; m = m_; dtype = dt; sparse = true;
         HIPC(hipSetDevice(device));
-        res = acquire_resources(device, 0);   // recycled stream + pinned block (qps_internal.h)
-        st = res.st;
-        prof.st = st;
+        st = prof.st = lease.acquire(device);   // recycled stream + pinned block (qps_internal.h)
+        void* const pinned = lease.res.pinned;
         up.reset(new StagedUploader(st));
         if (Pcp[n] - base > 2000000000LL || Acp[n] - base > 2000000000LL) throw QpsError(QPS_ERR_BAD_DIMENSION, "more than 2^31 non-zeros");
         // canonical host copies first (sorted rows, duplicates summed, 0-based: a C caller's CSC need not be what Julia's sparse() guarantees);
@@ -984,18 +984,18 @@ template <typename T> struct SparseSolver : SolverBase {
             build_blocked(PA, Sh);
         }
         const int64_t nn = n + 64, mm = m + 64;
-        q = dalloc<T>(nn, st); x = dalloc<T>(nn, st); xp = dalloc<T>(nn, st); xx = dalloc<T>(nn, st); tt = dalloc<T>(nn, st);
-        cu = dalloc<T>(nn, st); cu2 = dalloc<T>(nn, st); cr = dalloc<T>(nn, st); cc = dalloc<T>(nn, st); Px = dalloc<T>(nn, st); Aty = dalloc<T>(nn, st);
-        l = dalloc<T>(mm, st); u = dalloc<T>(mm, st); z = dalloc<T>(mm, st); zp = dalloc<T>(mm, st); y = dalloc<T>(mm, st); zz = dalloc<T>(mm, st);
-        w = dalloc<T>(mm, st); tm = dalloc<T>(mm, st); Ax = dalloc<T>(mm, st);
+        q = mem.dalloc<T>(nn, st); x = mem.dalloc<T>(nn, st); xp = mem.dalloc<T>(nn, st); xx = mem.dalloc<T>(nn, st); tt = mem.dalloc<T>(nn, st);
+        cu = mem.dalloc<T>(nn, st); cu2 = mem.dalloc<T>(nn, st); cr = mem.dalloc<T>(nn, st); cc = mem.dalloc<T>(nn, st); Px = mem.dalloc<T>(nn, st); Aty = mem.dalloc<T>(nn, st);
+        l = mem.dalloc<T>(mm, st); u = mem.dalloc<T>(mm, st); z = mem.dalloc<T>(mm, st); zp = mem.dalloc<T>(mm, st); y = mem.dalloc<T>(mm, st); zz = mem.dalloc<T>(mm, st);
+        w = mem.dalloc<T>(mm, st); tm = mem.dalloc<T>(mm, st); Ax = mem.dalloc<T>(mm, st);
         nb_n = (int)((n + 255) / 256);
         part_uc_cap = std::max(std::max(At.nblocks, P.nblocks), nb_n + (int)((m + 255) / 256)) + 64;
-        part_uc = dalloc<double>(part_uc_cap, st); part_rr = dalloc<double>(nb_n + 64, st);
-        state = reinterpret_cast<CgState*>(dalloc<double>(16, st));
-        state_host = reinterpret_cast<CgState*>(res.pinned);                          // pinned block: CG state | check results
-        scratch = dalloc<unsigned long long>(16, st); res_dev = dalloc<double>(16, st);
-        res_host = reinterpret_cast<double*>(reinterpret_cast<char*>(res.pinned) + 128);
-        stage = dalloc<double>(std::max(nn, mm) + 64, st);
+        part_uc = mem.dalloc<double>(part_uc_cap, st); part_rr = mem.dalloc<double>(nb_n + 64, st);
+        state = reinterpret_cast<CgState*>(mem.dalloc<double>(16, st));
+        state_host = reinterpret_cast<CgState*>(pinned);                              // pinned block: CG state | check results
+        scratch = mem.dalloc<unsigned long long>(16, st); res_dev = mem.dalloc<double>(16, st);
+        res_host = reinterpret_cast<double*>(static_cast<char*>(pinned) + 128);
+        stage = mem.dalloc<double>(std::max(nn, mm) + 64, st);
         upload_vec(qh, q, n); upload_vec(lh, l, m); upload_vec(uh, u, m);
         const double s = sizeof(T);
         auto spmv_bytes = [&](const Csr& M, int cols) { return (double)M.nnz * (s + 4) + M.nrows * 4.0 + s * (M.nrows + cols); };
@@ -1012,19 +1012,9 @@ template <typename T> struct SparseSolver : SolverBase {
     }
     ~SparseSolver() override {
         (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);
         drop_graphs();
-        if (cu2) (void)hipFree(cu2);
-        for (Csr* M_ : {&A, &At, &P, &PA, &Lm}) {
-            void* bp[] = {M_->brp, M_->bci, M_->bva, M_->task_ptr, M_->tasks, M_->partial, M_->lr_ptr, M_->lr_desc, M_->wg_ptr, M_->sl_off, M_->sl_perm, M_->s_cols, M_->s_vals, M_->src, M_->lsrc};
-            for (void* p : bp) if (p) (void)hipFree(p);
-        }
-        { void* lp[] = {Lm.rp, Lm.ci, Lm.va, Lm.rb, L_vP, L_vAA, L_dg}; for (void* p : lp) if (p) (void)hipFree(p); }
-        void* ptrs[] = {A.rp, A.ci, A.va, A.rb, At.rp, At.ci, At.va, At.rb, P.rp, P.ci, P.va, P.rb, q, l, u, x, xp, z, zp, y, xx, zz, w, tt, cu, cr, cc, tm,
-                        Ax, Px, Aty, part_uc, part_rr, state, scratch, res_dev, stage};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
         prof.release_events();
-        if (res.st) recycle_resources(device, res);
     }
 
     void spmv(const Csr& M, const T* xin, T* out, T a, const T* v0, T b0, const T* v1, T b1, const CgState* stt,
@@ -1290,11 +1280,11 @@ template <typename T> struct SparseSolver : SolverBase {
         else if (op == QPS_OP_PA) {
             if (PA.blocked) {                                                                       // the stacked product of a CG iteration, then its blocks added up
                 spmv_blk(PA, cu, nullptr);
-                T* both = dalloc<T>(n + m + 64, st);
+                DeviceOwner tmp_mem;
+                T* both = tmp_mem.dalloc<T>(n + m + 64, st);
                 hipLaunchKernelGGL((k_spmv_combine<T>), dim3((unsigned)((n + m + 255) / 256)), dim3(256), 0, st, (int)(n + m), static_cast<const T*>(PA.partial), PA.nblk, (int64_t)(n + m),
                                    T(1), (const T*)nullptr, 0, (int64_t)0, T(0), (const T*)nullptr, T(0), (const T*)nullptr, T(0), both, (const T*)nullptr, (double*)nullptr, (const CgState*)nullptr);
                 download_vec(both, out, n); download_vec(both + n, out + n, m);
-                (void)hipFree(both);
             } else {
                 spmv(P, cu, cc, T(1), nullptr, T(0), nullptr, T(0), nullptr); download_vec(cc, out, n);
                 if (m > 0) spmv(A, cu, tm, T(1), nullptr, T(0), nullptr, T(0), nullptr);
@@ -1343,8 +1333,8 @@ template <typename T> struct SparseSolver : SolverBase {
 // refinement against the unperturbed system.
 // =================================================================================================================
 template <typename T> struct SparseProxQpSolver : ProxQpBase {
-    std::unique_ptr<SparseSolver<T>> ss;          // P, G = [A; C] as CSR (G, G'), the L D L' plugin, the staging buffers
-    hipStream_t st = nullptr;
+    std::unique_ptr<SparseSolver<T>> ss;          // P, G = [A; C] as CSR (G, G'), the L D L' plugin, the staging buffers; owns the stream
+    DeviceOwner mem; hipStream_t st = nullptr;    // this solver's own buffers: gone before `ss` and its stream lease
     int mtot = 0;
     T *g = nullptr, *dual = nullptr, *slack = nullptr, *hvec = nullptr, *x = nullptr, *xx = nullptr, *v = nullptr, *de = nullptr, *di = nullptr;
     T *X1 = nullptr, *X2 = nullptr, *X3 = nullptr, *r1 = nullptr, *r2 = nullptr, *dx = nullptr, *dnu = nullptr, *zero_m = nullptr;
@@ -1376,11 +1366,11 @@ template <typename T> struct SparseProxQpSolver : ProxQpBase {
                                      Gnz.empty() ? dummy_d : Gnz.data(), qh, zeros.data(), zeros.data(), 0));
         st = ss->st;
         const int64_t nn = n + 64, mm = mtot + 64;
-        g = dalloc<T>(mm, st); dual = dalloc<T>(mm, st); slack = dalloc<T>(mm, st); hvec = dalloc<T>(mm, st); v = dalloc<T>(mm, st); de = dalloc<T>(mm, st); di = dalloc<T>(mm, st);
-        r2 = dalloc<T>(mm, st); dnu = dalloc<T>(mm, st); zero_m = dalloc<T>(mm, st);
-        x = dalloc<T>(nn, st); xx = dalloc<T>(nn, st); X1 = dalloc<T>(nn, st); X2 = dalloc<T>(nn, st); X3 = dalloc<T>(nn, st); r1 = dalloc<T>(nn, st); dx = dalloc<T>(nn, st);
-        slots = dalloc<unsigned long long>(16, st);
-        slots_host = reinterpret_cast<unsigned long long*>(ss->res.pinned);
+        g = mem.dalloc<T>(mm, st); dual = mem.dalloc<T>(mm, st); slack = mem.dalloc<T>(mm, st); hvec = mem.dalloc<T>(mm, st); v = mem.dalloc<T>(mm, st); de = mem.dalloc<T>(mm, st); di = mem.dalloc<T>(mm, st);
+        r2 = mem.dalloc<T>(mm, st); dnu = mem.dalloc<T>(mm, st); zero_m = mem.dalloc<T>(mm, st);
+        x = mem.dalloc<T>(nn, st); xx = mem.dalloc<T>(nn, st); X1 = mem.dalloc<T>(nn, st); X2 = mem.dalloc<T>(nn, st); X3 = mem.dalloc<T>(nn, st); r1 = mem.dalloc<T>(nn, st); dx = mem.dalloc<T>(nn, st);
+        slots = mem.dalloc<unsigned long long>(16, st);
+        slots_host = reinterpret_cast<unsigned long long*>(ss->lease.res.pinned);
         ss->upload_vec(gh.data(), g, mtot);
         layout::canonical_csc(n, P0cp.data(), P0ri.empty() ? dummy_i : P0ri.data(), Pnz, 0, kPcp, kPri, kPnz);
         if (me > 0) layout::canonical_csc(n, Acp, Ari, Anz, base, kAcp, kAri, kAnz);
@@ -1388,9 +1378,7 @@ template <typename T> struct SparseProxQpSolver : ProxQpBase {
     }
     ~SparseProxQpSolver() override {
         (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        void* ptrs[] = {g, dual, slack, hvec, x, xx, v, de, di, X1, X2, X3, r1, r2, dx, dnu, zero_m, slots};
-        for (void* p_ : ptrs) if (p_) (void)hipFree(p_);
+        (void)hipStreamSynchronize(st);
     }
     void drop_init_copies() {
         for (auto* vv : {&kPcp, &kPri, &kAcp, &kAri}) std::vector<int64_t>().swap(*vv);

@@ -5,6 +5,7 @@
 // There is NO CPU fallback: without a HIP device every entry point fails with QPS_ERR_NO_DEVICE.
 #include "ldl_symbolic.h"
 #include <atomic>
+#include <memory>
 #include <thread>
 
 #include "batch_schedule.h"
@@ -41,8 +42,10 @@ HandleResources acquire_resources(int device, size_t block_need) {
         std::lock_guard<std::mutex> lk(g_res_mu);
         if (device >= 0 && device < kMaxDevices && !g_res[device].empty()) { r = g_res[device].back(); g_res[device].pop_back(); }
     }
-    if (!r.st) HIPC(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
-    if (!r.pinned) HIPC(hipHostMalloc(&r.pinned, kPinnedBytes));
+    try {
+        if (!r.st) HIPC(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
+        if (!r.pinned) HIPC(hipHostMalloc(&r.pinned, kPinnedBytes));
+    } catch (...) { recycle_resources(device, r); throw; }   // (an entry without a pinned block is completed by its next user)
     if (r.block && (r.block_bytes < block_need || r.block_bytes > 4 * block_need + ((size_t)1 << 20))) { (void)hipFree(r.block); r.block = nullptr; r.block_bytes = 0; }
     return r;
 }
@@ -111,7 +114,8 @@ template <typename T> struct DenseSolver : SolverBase {
     T *x = nullptr, *xp = nullptr, *z = nullptr, *zp = nullptr, *y = nullptr, *xx = nullptr, *zz = nullptr, *tt = nullptr, *yv = nullptr;
     T *part = nullptr, *part2 = nullptr, *sw_part = nullptr, *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
     T* At = nullptr; void* small_out = nullptr; void* small_out_host = nullptr; bool small_ok = false;   // small-problem path
-    Arena arena; HandleResources res; double* stage_mat = nullptr; int64_t stage_mat_count = 0;
+    StreamLease lease; Arena arena;   // destroyed in reverse: the device block first, then the stream lease, then the base's Profiler
+    double* stage_mat = nullptr; int64_t stage_mat_count = 0;
     int pass_slabs = 0, pass_rpw = 0;   // fused-pass plan (0 slabs: shape not supported, unfused loop only)
     unsigned long long* scratch = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
     bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int fac_nb = 0;
@@ -180,11 +184,10 @@ template <typename T> struct DenseSolver : SolverBase {
             if (stage_mat_count > 0) stage_mat = ar.take<double>(stage_mat_count);
         };
         layout(arena);
-        res = acquire_resources(device, arena.planned());                    // stream, pinned block and maybe a recycled device block
-        st = res.st; prof.st = st;
-        try { arena.commit(st, res.block, res.block_bytes); }
-        catch (...) { recycle_resources(device, res); res = HandleResources(); st = nullptr; prof.st = nullptr; throw; }
-        res.block = nullptr;                                                  // owned by the arena from here on
+        st = prof.st = lease.acquire(device, arena.planned());                // stream, pinned block and maybe a recycled device block
+        HandleResources& res = lease.res;
+        char* const recycled = res.block; res.block = nullptr;                // owned by the arena from here on
+        arena.commit(st, recycled, res.block_bytes);
         layout(arena);
         res_host = reinterpret_cast<double*>(res.pinned);                     // one pinned block: check results | small-kernel report
         small_out_host = small_ok ? reinterpret_cast<char*>(res.pinned) + 16 * sizeof(double) : nullptr;
@@ -209,12 +212,11 @@ template <typename T> struct DenseSolver : SolverBase {
     }
     ~DenseSolver() override {
         (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        if (st) trsv_blocked_forget_stream(device, st);   // the stream goes back to the pool (or is destroyed): the sweep gate must not record on it
+        (void)hipStreamSynchronize(st);
+        trsv_blocked_forget_stream(device, st);   // the stream goes back to the pool (or is destroyed): the sweep gate must not record on it
         drop_graphs();
         prof.release_events();
-        res.block = arena.base; res.block_bytes = arena.bytes; arena.base = nullptr;
-        if (res.st) recycle_resources(device, res); else arena.release();
+        lease.res.block = arena.base; lease.res.block_bytes = arena.bytes; arena.base = nullptr;   // the block goes back with the lease
     }
 
     // host double array -> device T vector (zero padded allocation is preserved beyond `count`)
@@ -231,8 +233,8 @@ template <typename T> struct DenseSolver : SolverBase {
         }
         const int64_t budget = (int64_t)32 << 20;   // doubles per panel (256 MiB)
         int pc = (int)std::max<int64_t>(64, (budget / std::max(rows, 1)) / 64 * 64);
-        double* buf = nullptr;
-        HIPC(hipMalloc((void**)&buf, sizeof(double) * (size_t)rows * (size_t)std::min(pc, cols)));
+        DeviceOwner tmp_mem;
+        double* buf = tmp_mem.alloc<double>((int64_t)rows * std::min(pc, cols));
         FastUploader fu(st, device);                 // pinned ring filled by several host threads (qps_internal.h)
         for (int c0 = 0; c0 < cols; c0 += pc) {
             const int nc = std::min(pc, cols - c0);
@@ -241,7 +243,6 @@ template <typename T> struct DenseSolver : SolverBase {
             import_colmajor<T>(st, buf, rows, rows, nc, d + c0, ldd);
             HIPC(hipStreamSynchronize(st));
         }
-        HIPC(hipFree(buf));
     }
 
     DenseChol<T> chol() const { return {st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail}; }
@@ -543,7 +544,7 @@ struct BatchSolverBase {
 };
 
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
-    hipStream_t st = nullptr;
+    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
     int NP = 0, MP = 0, nb = 0, slabs = 0, rpw = 0, part_tiles = 0;
     T *A = nullptr, *P = nullptr, *q = nullptr, *l = nullptr, *u = nullptr, *PI = nullptr, *AA = nullptr, *M = nullptr, *S = nullptr,
       *tmp = nullptr, *dinv = nullptr;
@@ -559,8 +560,7 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
     BatchedDenseSolver(int dev, int cnt, int64_t n_, int64_t m_) {
         device = dev; n = n_; m = m_; count = cnt;
         HIPC(hipSetDevice(device));
-        HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        prof.st = st;
+        st = prof.st = lease.acquire(device);
         NP = roundup(n, 64); MP = roundup(m, 64);
         slabs = apass_plan<T>(NP, MP, &rpw, count);
         {   // algorithmic bytes per launch of the batched kernels: `count` times the single-QP figures
@@ -570,37 +570,26 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
         }
         part_tiles = gemv_cols_tiles(MP);
         const int64_t nn = (int64_t)NP * NP, c = count;
-        A = dalloc<T>(c * MP * NP, st); P = dalloc<T>(c * nn, st); PI = dalloc<T>(c * nn, st); AA = dalloc<T>(c * nn, st); M = dalloc<T>(c * nn, st);
-        S = dalloc<T>(c * nn, st); tmp = dalloc<T>(c * nn, st); dinv = dalloc<T>(c * (int64_t)(NP / 64) * 4096, st);
-        q = dalloc<T>(c * NP, st); l = dalloc<T>(c * MP, st); u = dalloc<T>(c * MP, st);
-        x = dalloc<T>(c * NP, st); xp = dalloc<T>(c * NP, st); xres = dalloc<T>(c * NP, st); xx = dalloc<T>(c * NP, st); tt = dalloc<T>(c * NP, st);
-        yv = dalloc<T>(c * NP, st); Px = dalloc<T>(c * NP, st); Aty = dalloc<T>(c * NP, st); z = dalloc<T>(c * MP, st); y = dalloc<T>(c * MP, st);
+        A = mem.dalloc<T>(c * MP * NP, st); P = mem.dalloc<T>(c * nn, st); PI = mem.dalloc<T>(c * nn, st); AA = mem.dalloc<T>(c * nn, st); M = mem.dalloc<T>(c * nn, st);
+        S = mem.dalloc<T>(c * nn, st); tmp = mem.dalloc<T>(c * nn, st); dinv = mem.dalloc<T>(c * (int64_t)(NP / 64) * 4096, st);
+        q = mem.dalloc<T>(c * NP, st); l = mem.dalloc<T>(c * MP, st); u = mem.dalloc<T>(c * MP, st);
+        x = mem.dalloc<T>(c * NP, st); xp = mem.dalloc<T>(c * NP, st); xres = mem.dalloc<T>(c * NP, st); xx = mem.dalloc<T>(c * NP, st); tt = mem.dalloc<T>(c * NP, st);
+        yv = mem.dalloc<T>(c * NP, st); Px = mem.dalloc<T>(c * NP, st); Aty = mem.dalloc<T>(c * NP, st); z = mem.dalloc<T>(c * MP, st); y = mem.dalloc<T>(c * MP, st);
         // polishing (one QP at a time) writes the slabs of a count = 1 pass plan, or the tiles of the column GEMV, into `part`:
         // count * slabs can be smaller than either (count = 3, NP = 2048: 246 < 256)
         int rpw1 = 0;
         const int64_t part_slabs = std::max<int64_t>(std::max<int64_t>(c * slabs, apass_plan<T>(NP, MP, &rpw1, 1)), std::max(part_tiles, 1));
-        part = dalloc<T>(part_slabs * NP, st); part2 = dalloc<T>(c * slabs * NP, st); part_tmp = dalloc<T>((int64_t)std::max(part_tiles, 1) * NP, st);
-        const int sw_slabs = sweep_fused_slabs<T>(NP, count); sw_part = dalloc<T>(c * std::max(sw_slabs, 1) * NP, st);
-        fail = dalloc<int>(count + 4, st); d_active = dalloc<int>(count + 4, st); d_rho = dalloc<double>(count + 4, st); d_rhorho = dalloc<double>(count + 4, st);
-        scratch = dalloc<unsigned long long>(16 * c, st); res_dev = dalloc<double>(8 * c, st);
-        HIPC(hipHostMalloc((void**)&res_host, 8 * c * sizeof(double)));
-        HIPC(hipHostMalloc((void**)&h_int, (count + 4) * sizeof(int)));
-        HIPC(hipHostMalloc((void**)&h_dbl, 2 * (count + 4) * sizeof(double)));
-        stage = dalloc<double>(std::max<int64_t>((int64_t)MP * NP, nn) + 64, st);
+        part = mem.dalloc<T>(part_slabs * NP, st); part2 = mem.dalloc<T>(c * slabs * NP, st); part_tmp = mem.dalloc<T>((int64_t)std::max(part_tiles, 1) * NP, st);
+        const int sw_slabs = sweep_fused_slabs<T>(NP, count); sw_part = mem.dalloc<T>(c * std::max(sw_slabs, 1) * NP, st);
+        fail = mem.dalloc<int>(count + 4, st); d_active = mem.dalloc<int>(count + 4, st); d_rho = mem.dalloc<double>(count + 4, st); d_rhorho = mem.dalloc<double>(count + 4, st);
+        scratch = mem.dalloc<unsigned long long>(16 * c, st); res_dev = mem.dalloc<double>(8 * c, st);
+        res_host = mem.pinned<double>(8 * c); h_int = mem.pinned<int>(count + 4); h_dbl = mem.pinned<double>(2 * (count + 4));
+        stage = mem.dalloc<double>(std::max<int64_t>((int64_t)MP * NP, nn) + 64, st);
     }
     ~BatchedDenseSolver() override {
         (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);
         prof.release_events();
-        void* ptrs[] = {A, P, q, l, u, PI, AA, M, S, tmp, dinv, x, xp, xres, z, y, xx, tt, yv, part, part2, part_tmp, sw_part, Px, Aty, fail, d_active,
-                        d_rho, d_rhorho, scratch, res_dev, stage};
-        for (void* p_ : ptrs) if (p_) (void)hipFree(p_);
-        if (res_host) (void)hipHostFree(res_host);
-        if (h_int) (void)hipHostFree(h_int);
-        if (h_dbl) (void)hipHostFree(h_dbl);
-        if (sb_args) (void)hipFree(sb_args);
-        if (sb_host) (void)hipHostFree(sb_host);
-        if (st) (void)hipStreamDestroy(st);
     }
     // Loading a batch: everything goes through ONE pinned ring (several host threads fill a half while the other half travels) and ONE device staging buffer,
     // all on the handle's stream -- the copy into `stage` for matrix k + 1 is ordered behind the import kernel that read matrix k, so nothing waits on the host until
@@ -681,7 +670,7 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
             // Small shapes: ONE workgroup per QP runs that QP's whole loop (register-resident kernel, k_small.hip); the host only
             // steps in when some QP wants a rho switch (refactor, relaunch from its own iteration) -- SolveQuadraticProgram.jl:45-71 per QP.
             const size_t ab = admm_small_args_bytes(), ob = admm_small_out_bytes();
-            if (!sb_args) { sb_args = dalloc<char>((int64_t)(ab + ob) * count + 64, st); HIPC(hipHostMalloc(&sb_host, (ab + ob) * (size_t)count + 64)); }
+            if (!sb_host) { sb_args = mem.dalloc<char>((int64_t)(ab + ob) * count + 64, st); sb_host = mem.pinned<char>((ab + ob) * (size_t)count + 64); }
             char* args_h = static_cast<char*>(sb_host); char* outs_h = args_h + ab * count;
             char* args_d = sb_args; char* outs_d = sb_args + ab * count;
             std::vector<int> it(count, 0);
@@ -871,10 +860,11 @@ int64_t dense_asymmetry(const double* P, int64_t n, int64_t ldp) {
     const int64_t f = first.load();
     return f == INT64_MAX ? -1 : f;
 }
-int check_device(int device) {
+// QPS_OK, or the code after fail_with (the creators validate their arguments before they ask, so that a CPU-only caller sees the same errors)
+int require_device(int device, const char* out_of_range = "device index out of range") {
     int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return QPS_ERR_NO_DEVICE;
-    if (device < 0 || device >= cnt) return QPS_ERR_BAD_ARGUMENT;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail_with(nullptr, QPS_ERR_NO_DEVICE, "no HIP device visible: libqps_hip has no CPU fallback");
+    if (device < 0 || device >= cnt) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, out_of_range);
     return QPS_OK;
 }
 
@@ -899,22 +889,14 @@ int validate_params(Handle* h, const qps_params* p) {
 
 SolverBase* make_dense(int device, int64_t n, int64_t m, int dtype, const double* P, int64_t ldp, const double* A, int64_t lda,
                        const double* q, const double* l, const double* u) {
-    if (dtype == QPS_F64) {
-        auto* s = new DenseSolver<double>(device, n, m, dtype);
-        try {
-            s->upload_matrix(P, ldp, (int)n, (int)n, s->P, s->NP);
-            s->upload_matrix(A, lda, (int)m, (int)n, s->A, s->NP);
-            s->upload_vec(q, s->q, n); s->upload_vec(l, s->l, m); s->upload_vec(u, s->u, m);
-        } catch (...) { delete s; throw; }
-        return s;
-    }
-    auto* s = new DenseSolver<float>(device, n, m, dtype);
-    try {
+    auto load = [&](auto s) -> SolverBase* {   // a unique_ptr: a throw while loading drops the solver
         s->upload_matrix(P, ldp, (int)n, (int)n, s->P, s->NP);
         s->upload_matrix(A, lda, (int)m, (int)n, s->A, s->NP);
         s->upload_vec(q, s->q, n); s->upload_vec(l, s->l, m); s->upload_vec(u, s->u, m);
-    } catch (...) { delete s; throw; }
-    return s;
+        return s.release();
+    };
+    if (dtype == QPS_F64) return load(std::make_unique<DenseSolver<double>>(device, n, m, dtype));
+    return load(std::make_unique<DenseSolver<float>>(device, n, m, dtype));
 }
 
 }  // namespace
@@ -958,10 +940,7 @@ QPS_API int32_t qps_create_dense(int64_t n, int64_t m, const double* P, int64_t 
         const int64_t bad = dense_asymmetry(P, n, ldp);                              // SolveQuadraticProgram.m:166-168
         if (bad >= 0) { char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)bad); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b); }
     }
-    // argument validation first (a CPU-only caller sees the same errors), the device last
-    int dc = check_device(device);
-    if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-    if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range");
+    if (const int dc = require_device(device)) return dc;
     Handle* h = new Handle(); h->n = n; h->m = m;
     int rc = guarded(nullptr, [&] { h->impl = make_dense(device, n, m, dtype, P, ldp, A, lda, q, l, u); });
     if (rc != QPS_OK) { delete h; return rc; }
@@ -993,10 +972,7 @@ QPS_API int32_t qps_create_csc(int64_t n, int64_t m, const int64_t* Pcp, const i
         if (src != QPS_OK) return src;
         if (bad >= 0) { char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)bad); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b); }
     }
-    // argument validation first (a CPU-only caller sees the same errors), the device last
-    int dc = check_device(device);
-    if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-    if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range");
+    if (const int dc = require_device(device)) return dc;
     Handle* h = new Handle(); h->n = n; h->m = m;
     int rc;
     if (dense_path) {
@@ -1099,25 +1075,22 @@ QPS_API int32_t qps_create_dense_batch(int64_t count, int64_t n, int64_t m, cons
         const int64_t b = first_bad.load();
         if (b != INT64_MAX) { char bf[160]; snprintf(bf, sizeof bf, "QP %lld of the batch: the matrix mP must be a symmetric positive definite matrix", (long long)b); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, bf); }
     }
-    // argument validation first (a CPU-only caller sees the same errors), the device last
-    int dc = check_device(device);
-    if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-    if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range");
+    if (const int dc = require_device(device)) return dc;
     Handle* h = new Handle(); h->n = n; h->m = m;
     int rpw = 0;
     const int NPb = roundup(n, 64), MPb = roundup(m, 64);
     const bool fusable = count > 1 && m > 0 && (dtype == QPS_F64 ? apass_plan<double>(NPb, MPb, &rpw, (int)count) : apass_plan<float>(NPb, MPb, &rpw, (int)count)) > 0;
     if (fusable) {
         int rc = guarded(nullptr, [&] {
-            auto load = [&](auto* s) {
-                h->fused_batch = s;
+            auto load = [&](auto s) {   // a unique_ptr: a throw while loading drops the solver
                 for (int64_t b = 0; b < count; ++b) s->load_problem((int)b, P + b * n * n, A + b * m * n, q + b * n, l + b * m, u + b * m);
                 s->finish_loading();
+                h->fused_batch = s.release();
             };
-            if (dtype == QPS_F64) load(new BatchedDenseSolver<double>(device, (int)count, n, m));
-            else load(new BatchedDenseSolver<float>(device, (int)count, n, m));
+            if (dtype == QPS_F64) load(std::make_unique<BatchedDenseSolver<double>>(device, (int)count, n, m));
+            else load(std::make_unique<BatchedDenseSolver<float>>(device, (int)count, n, m));
         });
-        if (rc != QPS_OK) { delete h->fused_batch; delete h; return rc; }
+        if (rc != QPS_OK) { delete h; return rc; }
         *out = reinterpret_cast<qps_handle>(h);
         return QPS_OK;
     }
@@ -1158,11 +1131,8 @@ QPS_API int32_t qps_solve_batch_multi(int64_t count, int64_t n, int64_t m, const
         const int rc = validate_params(nullptr, p);
         if (rc != QPS_OK) return rc;
     }
-    for (int w = 0; w < num_workers; ++w) {
-        const int dc = check_device(devices[w]);
-        if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-        if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range in the worker list");
-    }
+    for (int w = 0; w < num_workers; ++w)
+        if (const int dc = require_device(devices[w], "device index out of range in the worker list")) return dc;
     std::mutex err_mu; std::string err_msg; int err_code = QPS_OK;
     auto solve_range = [&](int w, int64_t b0, int64_t cnt) -> int {
         qps_handle h = nullptr;
@@ -1230,9 +1200,7 @@ QPS_API int32_t qps_proxqp_create_dense(int64_t n, int64_t me, int64_t mi, const
     if (!P || !q || (me > 0 && (!A || !b)) || (mi > 0 && (!C || !d))) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "NULL problem array");
     if (ldp < n || (me > 0 && lda < me) || (mi > 0 && ldc < mi)) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "leading dimension smaller than the row count");
     if (dtype != QPS_F64 && dtype != QPS_F32) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "unknown dtype");
-    int dc = check_device(device);
-    if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-    if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range");
+    if (const int dc = require_device(device)) return dc;
     for (int64_t j = 0; j < n; ++j) {
         if (!all_finite(P + j * ldp, n, false)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "P contains NaN/Inf");
         if (me > 0 && !all_finite(A + j * lda, me, false)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "A contains NaN/Inf");
@@ -1279,9 +1247,7 @@ QPS_API int32_t qps_proxqp_create_csc(int64_t n, int64_t me, int64_t mi, const i
         if (n > 2000000000LL || me + mi > 2000000000LL) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "problem too large");
         if (!all_finite(q, n, false) || (me > 0 && !all_finite(b, me, false)) || (mi > 0 && !all_finite(d, mi, false)))
             return fail_with(nullptr, QPS_ERR_NOT_FINITE, "q/b/d contain NaN/Inf");
-        int dc = check_device(device);
-        if (dc == QPS_ERR_NO_DEVICE) return fail_with(nullptr, dc, "no HIP device visible: libqps_hip has no CPU fallback");
-        if (dc != QPS_OK) return fail_with(nullptr, dc, "device index out of range");
+        if (const int dc = require_device(device)) return dc;
         Handle* h = new Handle(); h->n = n; h->m = me + mi;
         int rc = guarded(nullptr, [&] { h->proxqp = make_proxqp_sparse(device, n, me, mi, dtype, Pcp, Pri, Pnz, q, Acp, Ari, Anz, b, Ccp, Cri, Cnz, d, index_base); });
         if (rc != QPS_OK) { delete h; return rc; }

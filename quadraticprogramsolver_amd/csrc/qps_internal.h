@@ -89,12 +89,43 @@ struct ProfScope {
 // were bolted on afterwards, a fill could land after an import kernel of the solver stream had written the same buffer -- the
 // "Cholesky breakdown on a well-conditioned matrix" seen once -- and the first SpMV could read CSR arrays whose DMA had not
 // finished -- the run-to-run differences of CG iteration counts.)
-template <typename T> inline T* dalloc(int64_t count, hipStream_t st) {
-    T* p = nullptr; if (count < 64) count = 64;
-    HIPC(hipMalloc((void**)&p, sizeof(T) * (size_t)count));
-    HIPC(hipMemsetAsync(p, 0, sizeof(T) * (size_t)count, st));
-    return p;
-}
+//
+// Ownership rule: a handle's raw allocations belong to ONE DeviceOwner member, its stream and pinned block to ONE StreamLease member; the
+// solvers' T* members are non-owning names.  Declared lease first, owner second, they are destroyed buffers first, then the stream -- after
+// a destructor body that synchronised the stream, and equally when a constructor throws half way (no destructor body runs then; hipFree
+// itself waits for the device before it releases memory).
+struct DeviceOwner {
+    std::vector<void*> dev, host;
+    DeviceOwner() = default;
+    DeviceOwner(const DeviceOwner&) = delete;
+    DeviceOwner& operator=(const DeviceOwner&) = delete;
+    ~DeviceOwner() { for (void* p : dev) (void)hipFree(p); for (void* p : host) (void)hipHostFree(p); }
+    // uninitialised; the slot is recorded before it is filled, so a throw leaves nothing unowned
+    template <typename T> T* alloc(int64_t count) {
+        dev.push_back(nullptr);
+        HIPC(hipMalloc(&dev.back(), sizeof(T) * (size_t)count));
+        return static_cast<T*>(dev.back());
+    }
+    // at least 64 elements, zero-filled on `st`
+    template <typename T> T* dalloc(int64_t count, hipStream_t st) {
+        if (count < 64) count = 64;
+        T* p = alloc<T>(count);
+        HIPC(hipMemsetAsync(p, 0, sizeof(T) * (size_t)count, st));
+        return p;
+    }
+    template <typename T> T* pinned(size_t count) {
+        host.push_back(nullptr);
+        HIPC(hipHostMalloc(&host.back(), sizeof(T) * count));
+        return static_cast<T*>(host.back());
+    }
+    void release(void* p) {   // free one recorded pointer now
+        if (!p) return;
+        auto it = std::find(dev.begin(), dev.end(), p);
+        if (it != dev.end()) { (void)hipFree(p); dev.erase(it); return; }
+        it = std::find(host.begin(), host.end(), p);
+        if (it != host.end()) { (void)hipHostFree(p); host.erase(it); }
+    }
+};
 
 // Pageable host memory -> device, ordered on `st`: the bytes travel through a pinned double buffer; a half is reused only after the
 // copy that read it has completed (its event), so the caller's source may be freed as soon as copy() returns.
@@ -193,7 +224,9 @@ struct Arena {
         HIPC(hipMemsetAsync(base, 0, need, st));   // on the handle's stream: ordered before everything the handle enqueues later
         off = 0; planning = false;
     }
-    void release() { if (base) (void)hipFree(base); base = nullptr; }
+    Arena() = default;
+    Arena(const Arena&) = delete;
+    ~Arena() { if (base) (void)hipFree(base); }
 };
 
 // Per-device recycling of what a dense handle needs besides its data: the stream, the pinned read-back block and (for small
@@ -202,6 +235,15 @@ struct Arena {
 struct HandleResources { hipStream_t st = nullptr; void* pinned = nullptr; char* block = nullptr; size_t block_bytes = 0; };
 HandleResources acquire_resources(int device, size_t block_need);      // block may come back null (caller allocates)
 void recycle_resources(int device, HandleResources r);                  // stream must be idle
+// A handle's lease on them: empty until acquire(); given back, with the stream idle, when the handle goes -- or when its constructor throws
+struct StreamLease {
+    int device = 0; HandleResources res;
+    StreamLease() = default;
+    StreamLease(const StreamLease&) = delete;
+    StreamLease& operator=(const StreamLease&) = delete;
+    hipStream_t acquire(int dev, size_t block_need = 0) { device = dev; res = acquire_resources(dev, block_need); return res.st; }
+    ~StreamLease() { if (!res.st) return; (void)hipStreamSynchronize(res.st); recycle_resources(device, res); }
+};
 
 struct SolverBase {
     int device = 0; hipStream_t st = nullptr; int dtype = 0; int64_t n = 0, m = 0; bool sparse = false;

@@ -153,19 +153,13 @@ __global__ __launch_bounds__(256) void k_mr_update(int N, const MrState* __restr
 
 inline dim3 blocks(int n) { return dim3((unsigned)((std::max(n, 1) + 255) / 256)); }
 
-// Work space of one polishing call (freed on every exit path)
-template <typename T> struct PolishWork {
-    T* base = nullptr; double* pa = nullptr; double* pb = nullptr; MrState* state = nullptr; MrState* state_host = nullptr; int* counts = nullptr;
-    ~PolishWork() {
-        if (base) (void)hipFree(base); if (pa) (void)hipFree(pa); if (pb) (void)hipFree(pb); if (state) (void)hipFree(state);
-        if (counts) (void)hipFree(counts); if (state_host) (void)hipHostFree(state_host);
-    }
-};
+// MINRES scalars of one polishing call (non-owning: polish_with's DeviceOwner frees them on every exit path)
+struct PolishWork { double* pa = nullptr; double* pb = nullptr; MrState* state = nullptr; MrState* state_host = nullptr; };
 
 // tt = minres(KK, b, tol, maxit, x0 = tt): returns the flag (0 converged, 1 not)
 template <typename T>
 int minres_device(hipStream_t st, int N, const std::function<void(const T*, T, T*)>& matvec, T delta, const T* b, T* xsol, T* c, T* Ra, T* Rb,
-                  T* W[2], PolishWork<T>& wk, double tol, int maxit, int* iters, double* relres) {
+                  T* W[2], PolishWork& wk, double tol, int maxit, int* iters, double* relres) {
     const int nb = (N + 255) / 256;
     matvec(xsol, delta, c);                                                                        // KK x0
     hipLaunchKernelGGL((k_mr_begin<T>), dim3(nb), dim3(256), 0, st, N, b, c, Ra, Rb, W[0], W[1], wk.pa, wk.pb);
@@ -235,16 +229,16 @@ void polish_with(hipStream_t st, int64_t n, int64_t m, int NP, int MP, const T* 
     const double t0 = now_s();
     if (p.numItrPolish <= 0) { if (rep) *rep = r; return; }                                        // :292
     const int N = NP + MP;
-    PolishWork<T> wk;
-    wk.base = dalloc<T>((int64_t)10 * N + MP, st);
-    T* g = wk.base; T* t = g + N; T* tt = t + N; T* rhs = tt + N; T* c = rhs + N; T* Ra = c + N; T* Rb = Ra + N;
+    DeviceOwner mem; PolishWork wk;
+    T* g = mem.dalloc<T>((int64_t)10 * N + MP, st); T* t = g + N; T* tt = t + N; T* rhs = tt + N; T* c = rhs + N; T* Ra = c + N; T* Rb = Ra + N;
     T* W[3] = {Rb + N, Rb + 2 * (int64_t)N, Rb + 3 * (int64_t)N}; T* mask = Rb + 4 * (int64_t)N;
     const int nb = (N + 255) / 256;
-    wk.pa = dalloc<double>(nb, st); wk.pb = dalloc<double>(nb, st); wk.state = dalloc<MrState>(2, st); wk.counts = dalloc<int>(4, st);
-    HIPC(hipHostMalloc((void**)&wk.state_host, sizeof(MrState)));
-    hipLaunchKernelGGL((k_pol_setup<T>), blocks(std::max(NP, MP)), dim3(256), 0, st, (int)n, NP, (int)m, MP, q, l, u, y, mask, g, wk.counts);
+    wk.pa = mem.dalloc<double>(nb, st); wk.pb = mem.dalloc<double>(nb, st); wk.state = mem.dalloc<MrState>(2, st);
+    int* const counts_dev = mem.dalloc<int>(4, st);
+    wk.state_host = mem.pinned<MrState>(1);
+    hipLaunchKernelGGL((k_pol_setup<T>), blocks(std::max(NP, MP)), dim3(256), 0, st, (int)n, NP, (int)m, MP, q, l, u, y, mask, g, counts_dev);
     int counts[2] = {0, 0};
-    HIPC(hipMemcpyAsync(counts, wk.counts, sizeof(counts), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(counts, counts_dev, sizeof(counts), hipMemcpyDeviceToHost, st));
 
     std::function<void(const T*, T, T*)> matvec = [&](const T* v, T delta, T* out) { kmat(v, delta, out, mask, W[2]); };
     HIPC(hipMemsetAsync(t, 0, sizeof(T) * (size_t)N, st));                                          // :307

@@ -11,6 +11,7 @@
 // The dense convenience constructor's initialisation (:73-93: x, y from the equality-constrained KKT system) is done on the
 // device by the range-space method: x = -P^{-1}(q + A'y), (A P^{-1} A') y = -(b + A P^{-1} q).
 #include <algorithm>
+#include <memory>
 
 #include "dense_chol.h"
 #include "qps_internal.h"
@@ -37,7 +38,7 @@ template <typename T> __global__ void k_pq_lower(int NP, const T* __restrict__ s
 inline dim3 g1(int n) { return dim3((unsigned)((std::max(n, 1) + 255) / 256)); }
 
 template <typename T> struct ProxQpSolver : ProxQpBase {
-    hipStream_t st = nullptr; HandleResources res;
+    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers first, then the stream lease
     int NP = 0, MP = 0, MEP = 0, mtot = 0, nb = 0, part_tiles = 0;
     T *G = nullptr, *Aonly = nullptr, *P = nullptr, *q = nullptr, *g = nullptr, *dual = nullptr, *slack = nullptr, *x = nullptr;
     T *w = nullptr, *v = nullptr, *de = nullptr, *di = nullptr, *tt = nullptr, *yv = nullptr, *xx = nullptr, *part = nullptr, *sw_part = nullptr;
@@ -48,28 +49,24 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
     ProxQpSolver(int dev, int64_t n_, int64_t me_, int64_t mi_) {
         device = dev; n = n_; me = me_; mi = mi_;
         HIPC(hipSetDevice(device));
-        res = acquire_resources(device, 0);   // recycled stream + pinned block (qps_internal.h)
-        st = res.st;
+        st = lease.acquire(device);   // recycled stream + pinned block (qps_internal.h)
         mtot = (int)(me + mi);
         NP = roundup(n, 64); MP = roundup(mtot, 64); MEP = roundup(std::max<int64_t>(me, 1), 64);
         const int64_t nn = (int64_t)NP * NP;
-        G = dalloc<T>((int64_t)MP * NP, st); Aonly = dalloc<T>((int64_t)MEP * NP, st); P = dalloc<T>(nn, st); q = dalloc<T>(NP, st); x = dalloc<T>(NP, st);
-        g = dalloc<T>(MP, st); dual = dalloc<T>(MP, st); slack = dalloc<T>(MP, st); w = dalloc<T>(MP, st); v = dalloc<T>(MP, st); de = dalloc<T>(MP, st); di = dalloc<T>(MP, st);
-        tt = dalloc<T>(NP, st); yv = dalloc<T>(NP, st); xx = dalloc<T>(NP, st); X1 = dalloc<T>(NP, st); X2 = dalloc<T>(NP, st); X3 = dalloc<T>(NP, st);
+        G = mem.dalloc<T>((int64_t)MP * NP, st); Aonly = mem.dalloc<T>((int64_t)MEP * NP, st); P = mem.dalloc<T>(nn, st); q = mem.dalloc<T>(NP, st); x = mem.dalloc<T>(NP, st);
+        g = mem.dalloc<T>(MP, st); dual = mem.dalloc<T>(MP, st); slack = mem.dalloc<T>(MP, st); w = mem.dalloc<T>(MP, st); v = mem.dalloc<T>(MP, st); de = mem.dalloc<T>(MP, st); di = mem.dalloc<T>(MP, st);
+        tt = mem.dalloc<T>(NP, st); yv = mem.dalloc<T>(NP, st); xx = mem.dalloc<T>(NP, st); X1 = mem.dalloc<T>(NP, st); X2 = mem.dalloc<T>(NP, st); X3 = mem.dalloc<T>(NP, st);
         part_tiles = std::max(gemv_cols_tiles(MP), apass_proxqp_slabs<T>(NP, MP));
-        part = dalloc<T>((int64_t)std::max(part_tiles, 1) * NP, st);
-        sw_part = dalloc<T>((int64_t)std::max(sweep_fused_slabs<T>(NP), 1) * NP, st);
-        PI = dalloc<T>(nn, st); KK = dalloc<T>(nn, st); M = dalloc<T>(nn, st); S = dalloc<T>(nn, st); tmp = dalloc<T>(nn, st); dinv = dalloc<T>((int64_t)(NP / 64) * 4096, st);
-        fail = dalloc<int>(4, st); slots = dalloc<unsigned long long>(16, st);
-        slots_host = reinterpret_cast<unsigned long long*>(res.pinned);
-        stage = dalloc<double>(std::max<int64_t>((int64_t)MP * NP, nn) + 64, st);
+        part = mem.dalloc<T>((int64_t)std::max(part_tiles, 1) * NP, st);
+        sw_part = mem.dalloc<T>((int64_t)std::max(sweep_fused_slabs<T>(NP), 1) * NP, st);
+        PI = mem.dalloc<T>(nn, st); KK = mem.dalloc<T>(nn, st); M = mem.dalloc<T>(nn, st); S = mem.dalloc<T>(nn, st); tmp = mem.dalloc<T>(nn, st); dinv = mem.dalloc<T>((int64_t)(NP / 64) * 4096, st);
+        fail = mem.dalloc<int>(4, st); slots = mem.dalloc<unsigned long long>(16, st);
+        slots_host = reinterpret_cast<unsigned long long*>(lease.res.pinned);
+        stage = mem.dalloc<double>(std::max<int64_t>((int64_t)MP * NP, nn) + 64, st);
     }
     ~ProxQpSolver() override {
         (void)hipSetDevice(device);
-        if (st) (void)hipStreamSynchronize(st);
-        void* ptrs[] = {G, Aonly, P, q, g, dual, slack, x, w, v, de, di, tt, yv, xx, part, sw_part, PI, KK, M, S, tmp, dinv, X1, X2, X3, fail, slots, stage};
-        for (void* p_ : ptrs) if (p_) (void)hipFree(p_);
-        if (res.st) recycle_resources(device, res);
+        (void)hipStreamSynchronize(st);
     }
     void put_vec(const double* h, T* d, int64_t c) { HIPC(upload_staged<T>(st, stage, h, d, c)); }
     void get_vec(const T* d, double* h, int64_t c) { HIPC(download_staged<T>(st, stage, d, h, c)); }
@@ -213,10 +210,9 @@ template <typename T> struct ProxQpSolver : ProxQpBase {
 
 ProxQpBase* make_proxqp(int device, int64_t n, int64_t me, int64_t mi, int dtype, const double* P, int64_t ldp, const double* A, int64_t lda,
                         const double* b, const double* C, int64_t ldc, const double* d, const double* q) {
-    if (dtype == QPS_F64) { auto* s = new ProxQpSolver<double>(device, n, me, mi); try { s->load(P, ldp, A, lda, b, C, ldc, d, q); } catch (...) { delete s; throw; } return s; }
-    auto* s = new ProxQpSolver<float>(device, n, me, mi);
-    try { s->load(P, ldp, A, lda, b, C, ldc, d, q); } catch (...) { delete s; throw; }
-    return s;
+    auto make = [&](auto s) -> ProxQpBase* { s->load(P, ldp, A, lda, b, C, ldc, d, q); return s.release(); };   // a unique_ptr: a throw while loading drops the solver
+    if (dtype == QPS_F64) return make(std::make_unique<ProxQpSolver<double>>(device, n, me, mi));
+    return make(std::make_unique<ProxQpSolver<float>>(device, n, me, mi));
 }
 
 }  // namespace qps
