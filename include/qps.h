@@ -214,6 +214,21 @@ int32_t qps_create_dense_batch(int64_t count, int64_t n, int64_t m, const double
                                const double *l, const double *u, int32_t dtype, int32_t device, qps_handle *out);
 int32_t qps_solve_batch(qps_handle h, double *x_inout, const qps_params *params, qps_info *infos);
 
+/* Shared-matrix batch: `count` QPs on ONE P (n x n, ldp) and ONE A (m x n, lda), both column-major as for qps_create_dense, that differ in
+ * q [count][n], l [count][m] and u [count][m] only -- an MPC horizon re-solved every sample, a regularisation path, a scenario sweep.  The
+ * matrices are stored, factorised and streamed once for all columns.  The handle is a batch handle: qps_solve_batch (x_inout [count][n], infos
+ * [count]), qps_get_dual ([count][m]), qps_set_profiling, qps_kernel_times, qps_last_error and qps_destroy work on it, and column b behaves as
+ * a stand-alone qps_solve on (P, q_b, A, l_b, u_b): its own check every numItrConv iterations, its own flag, iteration count and residuals,
+ * x = the iterate at its own stopping iteration.  Arguments are validated as by qps_create_dense, for every column, before a device is needed.
+ * count is limited to 65535, as for qps_create_dense_batch (QPS_ERR_BAD_DIMENSION beyond).
+ * QPS_ERR_UNSUPPORTED (qps_last_error names the reason): m = 0 or n padded beyond 16384 (fp64) / 32768 (fp32) at creation; adptRho != 0 (one
+ * factor needs one rho), polish != 0 or a trsvBlock other than 0 or >= n at qps_solve_batch -- the handle stays usable afterwards.
+ * qps_update_shared_vectors replaces q, l and / or u of every column (a NULL pointer keeps the array); the factorisation does not depend on
+ * them, so a following qps_solve_batch with reuseFactor = 1 and unchanged (rho, sigma) does not factorise again. */
+int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t m, const double *P, int64_t ldp, const double *A, int64_t lda,
+                                      const double *q, const double *l, const double *u, int32_t dtype, int32_t device, qps_handle *out);
+int32_t qps_update_shared_vectors(qps_handle h, const double *q, const double *l, const double *u);
+
 /* The per-problem loop of RunBenchmarks.jl:88-104 sharded over the devices of ONE process ("one host thread + one stream per device", "work-stealing at
  * chunk boundaries").  `count` independent dense QPs of one shape, arrays stacked as for qps_create_dense_batch; `devices[num_workers]` lists the device of every worker
  * -- one host thread each; a device may be listed more than once (two workers sharing a card).  Every worker repeatedly takes the next range of QPs from a shared

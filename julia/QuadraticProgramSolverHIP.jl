@@ -338,3 +338,65 @@ function SolveQuadraticProgramBatch!(mX::Matrix{Float64}, vmP::Vector{Matrix{Flo
         ccall((:qps_destroy, LIBQPS), Int32, (Ptr{Cvoid},), h[])
     end
 end
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Shared-matrix batch: `count` QPs on ONE mP and ONE mA that differ in vQ, vL, vU only (an MPC horizon re-solved every sample,
+# a regularisation path, a scenario sweep).  mQ is n x count, mL / mU are m x count, mX is n x count (warm starts in, solutions
+# out).  The matrices are stored, factorised and streamed once for all columns; ρ is fixed (adptΡ is refused by the library).
+# SharedBatchCreate / SharedBatchUpdate! / SharedBatchSolve! / SharedBatchDestroy keep a handle across solves (new vectors,
+# reuseFactor = true: no second factorisation); SolveQuadraticProgramSharedBatch! is the one-shot form.
+# ---------------------------------------------------------------------------------------------------------------------
+struct SharedBatchHip          # the handle with the shape the library was given: every later array is checked against it
+    h::Ptr{Cvoid}
+    n::Int
+    m::Int
+    count::Int
+end
+
+function SharedBatchCreate(mP::Matrix{Float64}, mQ::Matrix{Float64}, mA::Matrix{Float64}, mL::Matrix{Float64}, mU::Matrix{Float64}; device = 0, dtype::Type = Float64)
+    n = size(mP, 1); m = size(mA, 1); count = size(mQ, 2)
+    size(mP, 2) == n || throw(DimensionMismatch("The matrix mP must be square"))
+    size(mA, 2) == n || throw(DimensionMismatch("The number of columns of mA must match mP"))
+    size(mQ, 1) == n || throw(DimensionMismatch("mQ must be n x count"))
+    (size(mL) == (m, count) && size(mU) == (m, count)) || throw(DimensionMismatch("mL and mU must be m x count"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mP mA mQ mL mU _check(ccall((:qps_create_dense_shared_batch, LIBQPS), Int32,
+        (Int64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ref{Ptr{Cvoid}}),
+        count, n, m, mP, max(n, 1), mA, max(m, 1), mQ, mL, mU, _dtype(dtype), Int32(device), h))
+    return SharedBatchHip(h[], n, m, count)
+end
+
+function SharedBatchUpdate!(sb::SharedBatchHip; mQ::Union{Nothing, Matrix{Float64}} = nothing, mL::Union{Nothing, Matrix{Float64}} = nothing,
+    mU::Union{Nothing, Matrix{Float64}} = nothing)
+    h = sb.h
+    (mQ === nothing || size(mQ) == (sb.n, sb.count)) || throw(DimensionMismatch("mQ must be n x count"))
+    (mL === nothing || size(mL) == (sb.m, sb.count)) || throw(DimensionMismatch("mL must be m x count"))
+    (mU === nothing || size(mU) == (sb.m, sb.count)) || throw(DimensionMismatch("mU must be m x count"))
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve mQ mL mU _check(ccall((:qps_update_shared_vectors, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                       h, p(mQ), p(mL), p(mU)), h)
+    return nothing
+end
+
+function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIterations = 5000, ϵAbs = 1e-6, ϵRel = 1e-6, ρ = 1, σ = 1e-6, α = 1.6,
+    numItrConv = 25, reuseFactor::Bool = false)
+    h = sb.h; count = sb.count
+    size(mX) == (sb.n, count) || throw(DimensionMismatch("mX must be n x count: the library reads and writes count columns of length n"))
+    prm = QpsParams(numIterations, 0, numItrConv, 10, 500, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, 1e-6, 5, 1e-6, 1e-6, 1000, 0, 0, 0)
+    buf = Vector{UInt8}(undef, count * sizeof(QpsInfo))
+    GC.@preserve mX buf _check(ccall((:qps_solve_batch, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
+                                     h, mX, Ref(prm), buf), h)
+    return [ConvergenceFlag(unsafe_load(Ptr{Int32}(pointer(buf) + (b - 1) * sizeof(QpsInfo)))) for b in 1:count]
+end
+
+SharedBatchDestroy(sb::SharedBatchHip) = ccall((:qps_destroy, LIBQPS), Int32, (Ptr{Cvoid},), sb.h)
+
+function SolveQuadraticProgramSharedBatch!(mX::Matrix{Float64}, mP::Matrix{Float64}, mQ::Matrix{Float64}, mA::Matrix{Float64}, mL::Matrix{Float64},
+    mU::Matrix{Float64}; device = 0, dtype::Type = Float64, kw...)
+    h = SharedBatchCreate(mP, mQ, mA, mL, mU; device = device, dtype = dtype)
+    try
+        return SharedBatchSolve!(h, mX; kw...)
+    finally
+        SharedBatchDestroy(h)
+    end
+end

@@ -1,0 +1,370 @@
+// k_shared.hip -- loop kernels of the shared-matrix batch (qps_create_dense_shared_batch): many QPs on ONE P and ONE A.
+//
+// With the matrices shared, every product of an ADMM iteration is "row-major matrix x 16-column panel": the matrix operand is streamed
+// once and serves all columns, the right-hand operand is a panel of 16 QPs.  That is the shape of v_mfma_f64_16x16x4_f64 /
+// v_mfma_f32_16x16x4_f32 (D[16 rows][16 QPs] += M[16 rows][4 k] * X[4 k][16 QPs]).
+//
+// State layout: a length-R vector of `count` QPs is a stack of panels [panel][row][16] (QP b = panel b / 16, column b % 16), rows padded like
+// the single-QP vectors (NP / MP), `count` padded to a multiple of 16 with columns that stay inactive and zero.
+//
+// One kernel, k_panel<T, TRI, EPI, PB, waves, staged>, does every product:
+//   * a workgroup of 8 (or 16) waves owns 16 matrix rows and PB panels; the k range of those rows is cut into steps of 32 columns dealt
+//     round-robin to the waves (wave w takes steps w, w + waves, ...), so a workgroup streams its rows front to back;
+//   * per step a lane loads 16 bytes per load instruction, non-temporal for the constraint matrix: whole 32-column rows of the tile (full
+//     cache lines), turned into the MFMA operand layout (row = lane & 15, k group = lane >> 4) through the wave's own LDS tile; matrices
+//     small enough to stay cached skip LDS and load in operand layout with 16 waves per workgroup.  The matching panel rows go straight
+//     into registers; the accumulators (PB tiles) stay in VGPRs; the next step's loads are issued before the current step's MFMAs (two
+//     register sets);
+//   * the partial tiles of the waves meet in LDS and are added in wave order -- every output element is its own dot product with a summation
+//     order that depends on the matrix shape only, never on `count` or on the QP's position: column b of a batch is bit-identical to the same
+//     data solved alone;
+//   * the row-wise part of the iteration runs as the epilogue on the summed tile (EPI), per column, honouring the active mask.
+// TRI: 0 full rows, 1 columns <= row (forward sweep over the sweep matrix S), 2 columns >= row (backward sweep).
+// No float atomics, no scratch; the check norms use the u64 atomicMax scheme of k_loop.hip with 16 slots per column.
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+
+#include "qps_kernels.h"
+
+namespace qps {
+
+namespace {
+
+typedef double sd4 __attribute__((ext_vector_type(4)));
+typedef float sf4 __attribute__((ext_vector_type(4)));
+
+template <typename T> struct PanelMfma;
+template <> struct PanelMfma<double> {
+    using acc_t = sd4;
+    static __device__ __forceinline__ acc_t run(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
+    static __device__ __forceinline__ int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
+};
+template <> struct PanelMfma<float> {
+    using acc_t = sf4;
+    static __device__ __forceinline__ acc_t run(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    // C/D layout of v_mfma_f32_16x16x4_f32: col = lane & 15, row = (lane >> 4) * 4 + reg
+    static __device__ __forceinline__ int row(int lane, int reg) { return (lane >> 4) * 4 + reg; }
+};
+
+__device__ __forceinline__ unsigned long long sh_absbits(double v) { return (unsigned long long)__double_as_longlong(fabs(v)); }
+__device__ __forceinline__ unsigned long long sh_umax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+// waves per workgroup (k split): 8, or 16 for matrices small enough to sit in the caches (shared_panel_small)
+constexpr int SH_KS = 32;     // matrix columns per step
+
+template <typename T, int TRI, int PB, bool STG>
+struct PanelStep {
+    static constexpr int VN = VecOf<T>::N;          // elements per 16-byte load
+    static constexpr int U = SH_KS / (4 * VN);      // 16-byte loads per matrix row and step
+    typedef T NV __attribute__((ext_vector_type(VN)));
+    using acc_t = typename PanelMfma<T>::acc_t;
+
+    static constexpr int LPR = SH_KS / VN;          // staged form: lanes per matrix row of a step (16 fp64, 8 fp32) ...
+    static constexpr int RPI = 64 / LPR;            // ... and rows per load instruction (RPI * U = 16)
+    static constexpr int LROW = SH_KS + 16 / (int)sizeof(T);   // LDS row stride of a staged tile (elements): 32 columns + 16 bytes
+
+    // Direct form (STG = false).  lane (lc = lane & 15, g = lane >> 4): matrix row r0 + lc, columns kc + 4 VN u + VN g + j -- the MFMA
+    // operand layout: one load instruction touches 16 rows x 64 B.
+    // Staged form (STG = true): load u of the wave covers rows RPI u + lane / LPR whole (SH_KS columns, full 128-byte lines: measured
+    // 4.7-5.0 TB/s against 3.8-3.9 TB/s for the 64-byte pieces on the n = 4096, m = 8192 passes); stage() turns the tile into the operand
+    // layout through the wave's own LDS tile.  arow points at the lane's first element either way.
+    // Both forms: panel rows of the same k, column lc.
+    static __device__ __forceinline__ void load(NV (&A)[U], T (&B)[PB][U][VN], const T* arow, const T* const (&bcol)[PB], int kc, int g, int64_t ld) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const NV* src = reinterpret_cast<const NV*>(STG ? arow + kc + (int64_t)(RPI * u) * ld : arow + kc + u * 4 * VN);
+            A[u] = (TRI == 0) ? __builtin_nontemporal_load(src) : *src;
+        }
+#pragma unroll
+        for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < VN; ++j) B[pb][u][j] = bcol[pb][(int64_t)(kc + u * 4 * VN + VN * g + j) * 16];
+    }
+    // staged tile -> operand layout through the wave's own LDS tile `t` (16 rows of LROW elements).  Only this wave touches `t` and a wave's
+    // LDS accesses execute in order, so no workgroup barrier is needed; the wave barriers keep the COMPILER from moving the reads (other lanes'
+    // data: no per-thread alias) above the writes, or the next step's writes above these reads.
+    static __device__ __forceinline__ void stage(NV (&A)[U], T* t, int lane) {
+        const int lc = lane & 15, g = lane >> 4;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int u = 0; u < U; ++u) *reinterpret_cast<NV*>(t + (RPI * u + lane / LPR) * LROW + VN * (lane % LPR)) = A[u];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int u = 0; u < U; ++u) A[u] = *reinterpret_cast<const NV*>(t + lc * LROW + 4 * VN * u + VN * g);
+    }
+    static __device__ __forceinline__ void mac(acc_t (&acc)[PB], NV (&A)[U], const T (&B)[PB][U][VN], int kc, int r0, int lc, int g) {
+        if (TRI != 0) {
+            // steps that touch the diagonal tile: the other triangle of S holds the mirrored factor, not zeros
+            const bool diag = (TRI == 1) ? (kc + SH_KS > r0) : (kc < r0 + 16);
+            if (diag) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int j = 0; j < VN; ++j) {
+                        const int c = kc + u * 4 * VN + VN * g + j, r = r0 + lc;
+                        const bool keep = (TRI == 1) ? (c <= r) : (c >= r);
+                        A[u][j] = keep ? A[u][j] : T(0);
+                    }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int j = 0; j < VN; ++j)
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb) acc[pb] = PanelMfma<T>::run(A[u][j], B[pb][u][j], acc[pb]);
+    }
+};
+
+// EPI: 0 out = s;  1 out = sigma x - q + s (right-hand side, LinearSystemSolvers.jl:136);  2 s = x~: out = s, xp = x, x = alpha s + (1 - alpha) x
+// (SolveQuadraticProgram.jl:56-57);  3 s = z~: zp = z, z = clamp(...), y += rho (...), w = rho z - y (:59-61 and the next :134-135)
+template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
+__global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
+    using S = PanelStep<T, TRI, PB, STG>;
+    using acc_t = typename S::acc_t;
+    typedef typename S::NV NV;
+    constexpr int VN = S::VN, U = S::U;
+    constexpr int RED = SH_NW * PB * 256, STAGE = STG ? SH_NW * 16 * S::LROW : 0;
+    __shared__ __attribute__((aligned(16))) T red[RED > STAGE ? RED : STAGE];   // the waves' staging tiles during the k loop, then the partial tiles
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, lc = lane & 15;
+    T* const tile = red + w * 16 * S::LROW;
+    // Workgroup id -> (row tile, panel group).  The groups of ONE row tile get ids 8 apart: ids are dealt round-robin over the 8 XCDs, so the
+    // workgroups that stream the same 16 rows for different panels run on one XCD at about the same time and share one trip to HBM.
+    const int nrt = a.rows / 16, npg = (a.npanel + PB - 1) / PB, full = (nrt & ~7) * npg, id = blockIdx.x;
+    int rt, pg;
+    if (id < full) { const int rem = id % (8 * npg); pg = rem >> 3; rt = id / (8 * npg) * 8 + (rem & 7); }
+    else { const int j = id - full, tail = nrt & 7; pg = j / tail; rt = (nrt & ~7) + j % tail; }
+    const int r0 = rt * 16, p0 = pg * PB;
+    int kbeg = 0, kend = a.K;
+    if (TRI == 1) kend = min(a.K, (r0 + 16 + SH_KS - 1) & ~(SH_KS - 1));
+    if (TRI == 2) kbeg = r0 & ~(SH_KS - 1);
+    const int nsteps = (kend - kbeg) / SH_KS;
+    const T* const arow = STG ? a.Mat + (int64_t)(r0 + lane / S::LPR) * a.ld + VN * (lane % S::LPR) : a.Mat + (int64_t)(r0 + lc) * a.ld + VN * g;
+    const T* bcol[PB];
+#pragma unroll
+    for (int pb = 0; pb < PB; ++pb) bcol[pb] = a.B + (int64_t)min(p0 + pb, a.npanel - 1) * a.K * 16 + lc;   // (a ragged last group repeats its last panel)
+    acc_t acc[PB];
+#pragma unroll
+    for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[pb][i] = T(0);
+    NV A0[U], A1[U];
+    T B0[PB][U][VN], B1[PB][U][VN];
+    int s = w;
+    if (s < nsteps) S::load(A0, B0, arow, bcol, kbeg + s * SH_KS, g, a.ld);
+    while (s < nsteps) {
+        int s1 = s + SH_NW;
+        if (s1 < nsteps) S::load(A1, B1, arow, bcol, kbeg + s1 * SH_KS, g, a.ld);
+        if (STG) S::stage(A0, tile, lane);
+        S::mac(acc, A0, B0, kbeg + s * SH_KS, r0, lc, g);
+        s = s1;
+        if (s >= nsteps) break;
+        s1 = s + SH_NW;
+        if (s1 < nsteps) S::load(A0, B0, arow, bcol, kbeg + s1 * SH_KS, g, a.ld);
+        if (STG) S::stage(A1, tile, lane);
+        S::mac(acc, A1, B1, kbeg + s * SH_KS, r0, lc, g);
+        s = s1;
+    }
+    if (STG) __syncthreads();   // every wave is done with its staging tile before the partial tiles overwrite them
+#pragma unroll
+    for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[(w * PB + pb) * 256 + PanelMfma<T>::row(lane, i) * 16 + lc] = acc[pb][i];
+    __syncthreads();
+    const T alpha1 = T(1) - a.alpha, rho1 = T(1) / a.rho;
+    for (int e = tid; e < PB * 256; e += SH_NW * 64) {
+        T sum = red[e];
+#pragma unroll
+        for (int ww = 1; ww < SH_NW; ++ww) sum += red[ww * PB * 256 + e];
+        const int pb = e >> 8, row = (e >> 4) & 15, col = e & 15;
+        const int P = p0 + pb;
+        if (P >= a.npanel) continue;
+        const int64_t idx = ((int64_t)P * a.rows + r0 + row) * 16 + col;
+        if (EPI == 0) a.out[idx] = sum;
+        else if (EPI == 1) a.out[idx] = sum + a.sigma * a.x[idx] - a.q[idx];
+        else if (EPI == 2) {
+            a.out[idx] = sum;
+            if (a.active[P * 16 + col]) {
+                const T xo = a.x[idx];
+                a.xp[idx] = xo;                                          // :56
+                a.x[idx] = a.alpha * sum + alpha1 * xo;                  // :57
+            }
+        } else {
+            if (a.active[P * 16 + col]) {
+                const T zo = a.z[idx], yo = a.y[idx];
+                a.zp[idx] = zo;                                          // :59
+                const T t = a.alpha * sum + alpha1 * zo + rho1 * yo;     // :60
+                const T lo = a.l[idx], hi = a.u[idx];
+                const T zn = t > hi ? hi : (t < lo ? lo : t);
+                const T yn = yo + a.rho * (a.alpha * sum + alpha1 * zo - zn);   // :61
+                a.z[idx] = zn; a.y[idx] = yn;
+                a.w[idx] = a.rho * zn - yn;                              // LinearSystemSolvers.jl:134-135 of the next iteration
+            }
+        }
+    }
+}
+
+// CheckConvergence (SolveQuadraticProgram.jl:79-112), per column: the nine inf-norms of k_check_norms over panels.
+// slots (16 per column): 0 ||Ax-z|| 1 ||Px+q+A'y|| 2 ||Ax|| 3 ||z|| 4 ||Px|| 5 ||A'y|| 6 ||q|| 7 ||x-xp|| 8 ||z-zp||
+template <typename T>
+__global__ __launch_bounds__(256) void k_shared_norms(int n, int m, int NP, int MP, const T* __restrict__ Ax, const T* __restrict__ Px, const T* __restrict__ Aty,
+                                                      const T* __restrict__ q, const T* __restrict__ x, const T* __restrict__ xp, const T* __restrict__ z,
+                                                      const T* __restrict__ zp, unsigned long long* __restrict__ slots) {
+    const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int64_t on = (int64_t)P * NP * 16 + col, om = (int64_t)P * MP * 16 + col;
+    unsigned long long v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = 0ull;
+    for (int r = blockIdx.x * 16 + rl; r < max(n, m); r += gridDim.x * 16) {
+        if (r < m) {
+            const int64_t i = om + (int64_t)r * 16;
+            v[0] = sh_umax(v[0], sh_absbits((double)(Ax[i] - z[i])));   // differences are formed in T (k_loop.hip)
+            v[2] = sh_umax(v[2], sh_absbits((double)Ax[i]));
+            v[3] = sh_umax(v[3], sh_absbits((double)z[i]));
+            v[8] = sh_umax(v[8], sh_absbits((double)(z[i] - zp[i])));
+        }
+        if (r < n) {
+            const int64_t i = on + (int64_t)r * 16;
+            v[1] = sh_umax(v[1], sh_absbits((double)(Px[i] + q[i] + Aty[i])));
+            v[4] = sh_umax(v[4], sh_absbits((double)Px[i]));
+            v[5] = sh_umax(v[5], sh_absbits((double)Aty[i]));
+            v[6] = sh_umax(v[6], sh_absbits((double)q[i]));
+            v[7] = sh_umax(v[7], sh_absbits((double)(x[i] - xp[i])));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        v[k] = sh_umax(v[k], __shfl_xor(v[k], 16));
+        v[k] = sh_umax(v[k], __shfl_xor(v[k], 32));
+        if ((threadIdx.x & 63) < 16 && v[k] != 0ull) atomicMax(&slots[(int64_t)(P * 16 + col) * 16 + k], v[k]);
+    }
+}
+
+__device__ __forceinline__ double sh_jmax(double a, double b) { return (isnan(a) || isnan(b)) ? (double)NAN : (a > b ? a : b); }
+
+// the decision of k_check_decide for every active column (fixed rho: the proposal stays rho); res: 8 doubles per column
+__global__ void k_shared_decide(int cols, const unsigned long long* __restrict__ slots, double* __restrict__ res, const int* __restrict__ active,
+                                double epsAbs, double epsRel, double epsAdmm, double rho) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= cols || !active[b]) return;
+    slots += (int64_t)b * 16; res += (int64_t)b * 8;
+    double nv[9];
+    for (int k = 0; k < 9; ++k) nv[k] = __longlong_as_double((long long)slots[k]);
+    const double normResPrim = nv[0], normResDual = nv[1];                 // :85-86
+    const double maxNormPrim = sh_jmax(nv[2], nv[3]);                       // :88
+    const double maxNormDual = sh_jmax(sh_jmax(nv[4], nv[5]), nv[6]);       // :89
+    const double epsPrim = epsAbs + epsRel * maxNormPrim;                   // :99
+    const double epsDual = epsAbs + epsRel * maxNormDual;                   // :100
+    int flag = 1;
+    if ((normResPrim < epsPrim) && (normResDual < epsDual)) flag = 3;       // :102-104
+    if ((nv[7] <= epsAdmm) && (nv[8] <= epsAdmm)) flag = 2;                 // :105-107 (not else)
+    res[0] = normResPrim; res[1] = normResDual; res[2] = maxNormPrim; res[3] = maxNormDual;
+    res[4] = rho; res[5] = (double)flag; res[6] = nv[7]; res[7] = nv[8];
+}
+
+// host layout [count][len] doubles <-> panels [panel][rowsP][16] of T
+template <typename T>
+__global__ void k_to_panels(const double* __restrict__ src, int count, int len, int rowsP, T* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)count * len) return;
+    const int b = (int)(i / len), r = (int)(i % len);
+    dst[((int64_t)(b >> 4) * rowsP + r) * 16 + (b & 15)] = (T)src[i];
+}
+template <typename T>
+__global__ void k_from_panels(const T* __restrict__ src, int count, int len, int rowsP, double* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)count * len) return;
+    const int b = (int)(i / len), r = (int)(i % len);
+    dst[i] = (double)src[((int64_t)(b >> 4) * rowsP + r) * 16 + (b & 15)];
+}
+
+// dst (cols x rows, ld ldd) = src' (rows x cols, ld lds); rows, cols multiples of 32
+template <typename T>
+__global__ __launch_bounds__(256) void k_transpose(const T* __restrict__ src, int64_t lds, T* __restrict__ dst, int64_t ldd) {
+    __shared__ T tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tile[ty + 8 * k][tx] = src[(int64_t)(r0 + ty + 8 * k) * lds + c0 + tx];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[(int64_t)(c0 + ty + 8 * k) * ldd + r0 + tx] = tile[tx][ty + 8 * k];
+}
+
+template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
+void panel_launch(hipStream_t st, const PanelArgs<T>& a) {
+    const dim3 grid((a.rows / 16) * ((a.npanel + PB - 1) / PB)), block(SH_NW * 64);
+    if (g_launch_timing.start) {   // profiled launch: the dispatch's own timestamps (qps_kernels.h)
+        const LaunchTiming lt = g_launch_timing;
+        g_launch_timing = LaunchTiming();
+        hipExtLaunchKernelGGL((k_panel<T, TRI, EPI, PB, SH_NW, STG>), grid, block, 0, st, lt.start, lt.stop, 0, a);
+        return;
+    }
+    hipLaunchKernelGGL((k_panel<T, TRI, EPI, PB, SH_NW, STG>), grid, block, 0, st, a);
+}
+template <typename T, int TRI, int EPI>
+void panel_shape(hipStream_t st, const PanelArgs<T>& a) {
+    // The shape of the launch depends on the MATRIX only, so a column sees the same summation order whatever the batch around it is.
+    if (shared_panel_small(a.rows, a.K, sizeof(T))) { panel_launch<T, TRI, EPI, 1, 16, false>(st, a); return; }
+    if (a.npanel >= 2) panel_launch<T, TRI, EPI, 2, 8, true>(st, a); else panel_launch<T, TRI, EPI, 1, 8, true>(st, a);
+}
+
+}  // namespace
+
+// Matrices of at most 32 MiB stay in L2 / Infinity Cache between launches: the launch is then bound by the chain of dependent loads of a wave, not
+// by bytes -- one panel per workgroup (twice the workgroups, the matrix re-read from cache per panel) and 16 waves per workgroup halve that chain.
+bool shared_panel_small(int rows, int K, size_t elem) { return (size_t)rows * (size_t)K * elem <= ((size_t)32 << 20); }
+
+template <typename T>
+void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a) {
+    switch (op) {
+        case SharedPanelOp::product: panel_shape<T, 0, 0>(st, a); break;
+        case SharedPanelOp::rhs: panel_shape<T, 0, 1>(st, a); break;
+        case SharedPanelOp::forward: panel_shape<T, 1, 0>(st, a); break;
+        case SharedPanelOp::backward_x: panel_shape<T, 2, 2>(st, a); break;
+        case SharedPanelOp::rows_zy: panel_shape<T, 0, 3>(st, a); break;
+    }
+}
+
+template <typename T>
+void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* Ax, const T* Px, const T* Aty, const T* q, const T* x, const T* xp,
+                  const T* z, const T* zp, unsigned long long* slots, double* res_dev, const int* active, double epsAbs, double epsRel, double epsAdmm,
+                  double rho) {
+    const int blocks = std::max(1, std::min((std::max(n, m) + 15) / 16, 256));
+    hipLaunchKernelGGL((k_shared_norms<T>), dim3(blocks, npanel), dim3(256), 0, st, n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots);
+    hipLaunchKernelGGL(k_shared_decide, dim3((npanel * 16 + 63) / 64), dim3(64), 0, st, npanel * 16, slots, res_dev, active, epsAbs, epsRel, epsAdmm, rho);
+}
+
+template <typename T> void to_panels(hipStream_t st, const double* src, int count, int len, int rowsP, T* dst) {
+    const int64_t total = (int64_t)count * len;
+    if (total <= 0) return;
+    hipLaunchKernelGGL((k_to_panels<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, count, len, rowsP, dst);
+}
+template <typename T> void from_panels(hipStream_t st, const T* src, int count, int len, int rowsP, double* dst) {
+    const int64_t total = (int64_t)count * len;
+    if (total <= 0) return;
+    hipLaunchKernelGGL((k_from_panels<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, count, len, rowsP, dst);
+}
+template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int64_t lds, int rows, int cols, T* dst, int64_t ldd) {
+    hipLaunchKernelGGL((k_transpose<T>), dim3(cols / 32, rows / 32), dim3(256), 0, st, src, lds, dst, ldd);
+}
+
+#define INST(T)                                                                                                                         \
+    template void shared_panel<T>(hipStream_t, SharedPanelOp, const PanelArgs<T>&);                                                     \
+    template void shared_check<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,     \
+                                  const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double);        \
+    template void to_panels<T>(hipStream_t, const double*, int, int, int, T*);                                                          \
+    template void from_panels<T>(hipStream_t, const T*, int, int, int, double*);                                                        \
+    template void transpose_rowmajor<T>(hipStream_t, const T*, int64_t, int, int, T*, int64_t);
+INST(double)
+INST(float)
+#undef INST
+
+}  // namespace qps

@@ -104,6 +104,24 @@ namespace {
 
 thread_local std::string g_last_error;
 
+// column-major host matrix (rows x cols, ld ldh) -> row-major device T (ld ldd), streamed through a bounded device staging buffer in column panels
+template <typename T>
+void upload_matrix_panels(hipStream_t st, int device, const double* h, int64_t ldh, int rows, int cols, T* d, int64_t ldd) {
+    if (rows <= 0 || cols <= 0) return;
+    const int64_t budget = (int64_t)32 << 20;   // doubles per panel (256 MiB)
+    int pc = (int)std::max<int64_t>(64, (budget / std::max(rows, 1)) / 64 * 64);
+    DeviceOwner tmp_mem;
+    double* buf = tmp_mem.alloc<double>((int64_t)rows * std::min(pc, cols));
+    FastUploader fu(st, device);                 // pinned ring filled by several host threads (qps_internal.h)
+    for (int c0 = 0; c0 < cols; c0 += pc) {
+        const int nc = std::min(pc, cols - c0);
+        if (ldh == rows) fu.copy(buf, h + (int64_t)c0 * ldh, sizeof(double) * (size_t)rows * (size_t)nc);
+        else for (int c = 0; c < nc; ++c) fu.copy(buf + (int64_t)c * rows, h + (int64_t)(c0 + c) * ldh, sizeof(double) * (size_t)rows);
+        import_colmajor<T>(st, buf, rows, rows, nc, d + c0, ldd);
+        HIPC(hipStreamSynchronize(st));
+    }
+}
+
 // =================================================================================================================
 // Dense problem, Cholesky path
 // =================================================================================================================
@@ -231,18 +249,7 @@ template <typename T> struct DenseSolver : SolverBase {
             HIPC(hipStreamSynchronize(st));
             return;
         }
-        const int64_t budget = (int64_t)32 << 20;   // doubles per panel (256 MiB)
-        int pc = (int)std::max<int64_t>(64, (budget / std::max(rows, 1)) / 64 * 64);
-        DeviceOwner tmp_mem;
-        double* buf = tmp_mem.alloc<double>((int64_t)rows * std::min(pc, cols));
-        FastUploader fu(st, device);                 // pinned ring filled by several host threads (qps_internal.h)
-        for (int c0 = 0; c0 < cols; c0 += pc) {
-            const int nc = std::min(pc, cols - c0);
-            if (ldh == rows) fu.copy(buf, h + (int64_t)c0 * ldh, sizeof(double) * (size_t)rows * (size_t)nc);
-            else for (int c = 0; c < nc; ++c) fu.copy(buf + (int64_t)c * rows, h + (int64_t)(c0 + c) * ldh, sizeof(double) * (size_t)rows);
-            import_colmajor<T>(st, buf, rows, rows, nc, d + c0, ldd);
-            HIPC(hipStreamSynchronize(st));
-        }
+        upload_matrix_panels<T>(st, device, h, ldh, rows, cols, d, ldd);
     }
 
     DenseChol<T> chol() const { return {st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail}; }
@@ -541,6 +548,7 @@ struct BatchSolverBase {
     virtual ~BatchSolverBase() {}
     virtual void solve_batch(double* x, const qps_params& p, qps_info* infos) = 0;
     virtual void get_dual(double* z, double* y) = 0;   // [count][m] each
+    virtual bool update_vectors(const double* q, const double* l, const double* u) { (void)q; (void)l; (void)u; return false; }   // shared-matrix batches only
 };
 
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
@@ -790,6 +798,180 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
                 in.trsvBlock = nb; in.sweepVariant = chol_sweep_variant<T>(NP, nb);
                 in.sweepGaveUp = 0; in.cgExplicit = 0;
             }
+        }
+    }
+};
+
+// =================================================================================================================
+// Shared-matrix batch: `count` QPs on ONE P and ONE A that differ in q, l, u only (an MPC horizon re-solved every sample, a regularisation
+// path, a scenario sweep).  One copy of every matrix, one factorisation, one sweep matrix with a single inverted block; the state lives in
+// 16-column panels and every product of the loop is a row-major matrix times panels on the MFMA pipe (k_shared.hip), so a matrix is read once
+// per launch whatever `count` is.  Per iteration: A' (a row-major copy of the transpose), the lower and the upper triangle of S, A.
+// rho is fixed (a common factor needs a common rho); every column keeps its own check, flag, stopping iteration and residuals, and a column
+// that stopped is frozen by the active mask, exactly as BatchedDenseSolver does.
+// =================================================================================================================
+template <typename T> inline int shared_batch_max_np() { return 16 * 512 * VecOf<T>::N; }   // whole-factor explicit inverse: 16384 fp64 / 32768 fp32 (k_trsv.hip)
+
+template <typename T> struct SharedBatchSolver : BatchSolverBase {
+    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
+    int NP = 0, MP = 0, CP = 0, npanel = 0, nb = 0;
+    T *A = nullptr, *At = nullptr, *P = nullptr, *PI = nullptr, *AA = nullptr, *M = nullptr, *S = nullptr, *tmp = nullptr, *dinv = nullptr;
+    T *q = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *xp = nullptr, *xx = nullptr, *tt = nullptr, *yv = nullptr, *z = nullptr, *zp = nullptr,
+      *y = nullptr, *w = nullptr, *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
+    int* fail = nullptr; int* d_active = nullptr; int* h_int = nullptr;
+    unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
+    bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
+    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0;
+    std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
+
+    SharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_) {
+        device = dev; n = n_; m = m_; count = cnt;
+        HIPC(hipSetDevice(device));
+        st = prof.st = lease.acquire(device);
+        NP = roundup(n, 64); MP = roundup(m, 64); CP = roundup(count, 16); npanel = CP / 16;
+        nb = pick_nb<T>(32768, NP);   // one inverted block over the whole factor
+        const int64_t nn = (int64_t)NP * NP, mn = (int64_t)MP * NP, pn = (int64_t)CP * NP, pm = (int64_t)CP * MP;
+        A = mem.dalloc<T>(mn, st); At = mem.dalloc<T>(mn, st); P = mem.dalloc<T>(nn, st); PI = mem.dalloc<T>(nn, st); AA = mem.dalloc<T>(nn, st);
+        M = mem.dalloc<T>(nn, st); S = mem.dalloc<T>(nn, st); tmp = mem.dalloc<T>(nn, st); dinv = mem.dalloc<T>((int64_t)(NP / 64) * 4096, st);
+        q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); xx = mem.dalloc<T>(pn, st); tt = mem.dalloc<T>(pn, st);
+        yv = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
+        l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st);
+        w = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
+        fail = mem.dalloc<int>(4, st); d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
+        slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
+        stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
+        // algorithmic bytes per launch: the matrix once, the panels it reads and writes
+        const double s = sizeof(T), c = CP;
+        cat_atw = prof.category("shared: A'w + rhs (MFMA panels)", s * ((double)m * n + c * (m + 3.0 * n)));
+        cat_fwd = prof.category("shared: forward sweep (MFMA panels)", s * ((double)n * (n + 1) / 2 + 2.0 * c * n));
+        cat_bwd = prof.category("shared: backward sweep + x (MFMA panels)", s * ((double)n * (n + 1) / 2 + 5.0 * c * n));
+        cat_pass = prof.category("shared: A x~ + row updates (MFMA panels)", s * ((double)m * n + c * (n + 8.0 * m)));
+        cat_chk = prof.category("shared: check (A x, P x, A'y, norms)", s * (2.0 * m * n + (double)n * n + c * (8.0 * n + 6.0 * m)));
+    }
+    ~SharedBatchSolver() override {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(st);
+        prof.release_events();
+    }
+    // host [count][len] doubles -> panels (padding rows and columns zero); ordered on the stream, the host array is free when this returns
+    void put_panels(const double* h, T* d, int64_t len, int rowsP) {
+        HIPC(hipMemsetAsync(d, 0, sizeof(T) * (size_t)CP * rowsP, st));
+        if (!up) up.reset(new StagedUploader(st));   // its pinned double buffer lives as long as the handle: every solve uploads warm starts
+        up->copy(stage, h, sizeof(double) * (size_t)count * (size_t)len);
+        to_panels<T>(st, stage, count, (int)len, rowsP, d);
+        HIPC(hipStreamSynchronize(st));
+    }
+    void get_panels(const T* d, double* h, int64_t len, int rowsP) {
+        from_panels<T>(st, d, count, (int)len, rowsP, stage);
+        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count * (size_t)len, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    void load(const double* Ph, int64_t ldp, const double* Ah, int64_t lda, const double* qh, const double* lh, const double* uh) {
+        upload_matrix_panels<T>(st, device, Ph, ldp, (int)n, (int)n, P, NP);
+        upload_matrix_panels<T>(st, device, Ah, lda, (int)m, (int)n, A, NP);
+        transpose_rowmajor<T>(st, A, NP, MP, NP, At, MP);   // row-major A': every product of the loop is "row-major matrix x panel"
+        update_vectors(qh, lh, uh);
+    }
+    bool update_vectors(const double* qh, const double* lh, const double* uh) override {
+        HIPC(hipSetDevice(device));
+        if (qh) put_panels(qh, q, n, NP);
+        if (lh) put_panels(lh, l, m, MP);
+        if (uh) put_panels(uh, u, m, MP);
+        return true;   // the factor depends on P, A, rho, sigma only: it stays valid
+    }
+    void get_dual(double* zh, double* yh) override {
+        HIPC(hipSetDevice(device));
+        if (zh) get_panels(z, zh, m, MP);
+        if (yh) get_panels(y, yh, m, MP);
+    }
+    // LinSysSolInit once for all columns: LinearSystemSolvers.jl:110-122 + factorisation, sweep matrix with one inverted block
+    void factorize(double rho, double sigma, bool rebuild_all) {
+        const bool rebuild = rebuild_all || !have_AA;
+        const DenseChol<T> c{st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail};
+        factor_valid = false;
+        HIPC(hipMemsetAsync(fail, 0, sizeof(int) * 4, st));
+        c.form(sigma, rho, rebuild, rebuild);
+        have_AA = true;
+        c.factor(nb);
+        char ctx[128]; snprintf(ctx, sizeof ctx, "rho=%g, sigma=%g; factorisation #%d of this handle", rho, sigma, ++num_factorizations);
+        c.check("P + sigma I + rho A'A", ctx, h_int);
+        factor_valid = true; fac_rho = rho; fac_sigma = sigma;
+    }
+    PanelArgs<T> product_args(const T* Mat, int64_t ld, int rows, int K, const T* B, T* out) const {
+        PanelArgs<T> a; a.Mat = Mat; a.ld = ld; a.rows = rows; a.K = K; a.B = B; a.npanel = npanel; a.out = out; a.active = d_active;
+        return a;
+    }
+
+    void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
+        HIPC(hipSetDevice(device));
+        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: adptRho is not supported (one factor serves every column, so rho is common and fixed)");
+        if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: polishing is not supported");
+        if (p.trsvBlock != 0 && p.trsvBlock < n)
+            throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: trsvBlock must be 0 or >= n (the sweeps run over one inverted block covering the whole factor)");
+        if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: QPS_LINSYS_CHOLESKY only");
+        const double t0 = now_s();
+        const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
+        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
+        const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
+        if (!reuse) factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma);        // :36
+        put_panels(xh, x, n, NP);
+        for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
+        for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st));     // :39-41
+        std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
+        std::vector<double> resP(count, NAN), resD(count, NAN);
+        for (int b = 0; b < count; ++b) active[b] = 1;
+        auto push_active = [&] {
+            for (int b = 0; b < CP; ++b) h_int[b] = active[b];
+            HIPC(hipMemcpyAsync(d_active, h_int, sizeof(int) * CP, hipMemcpyHostToDevice, st));
+            HIPC(hipStreamSynchronize(st));   // the pinned staging is reused
+        };
+        push_active();
+        const double t1 = now_s();
+        PanelArgs<T> a_rhs = product_args(At, MP, NP, MP, w, tt); a_rhs.x = x; a_rhs.q = q; a_rhs.sigma = (T)sigma;
+        PanelArgs<T> a_fwd = product_args(S, NP, NP, NP, tt, yv);
+        PanelArgs<T> a_bwd = product_args(S, NP, NP, NP, yv, xx); a_bwd.x = x; a_bwd.xp = xp; a_bwd.alpha = (T)alpha;
+        PanelArgs<T> a_row = product_args(A, NP, MP, NP, xx, nullptr);
+        a_row.z = z; a_row.zp = zp; a_row.y = y; a_row.w = w; a_row.l = l; a_row.u = u; a_row.alpha = (T)alpha; a_row.rho = (T)rho;
+        const PanelArgs<T> a_ax = product_args(A, NP, MP, NP, x, Ax), a_px = product_args(P, NP, NP, NP, x, Px), a_aty = product_args(At, MP, NP, MP, y, Aty);
+        int nactive = count;
+        for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
+            const int lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one launch of each kernel in 50 iterations
+            { ProfLaunchScope ps(prof, cat_atw, lvl); shared_panel<T>(st, SharedPanelOp::rhs, a_rhs); }          // LinearSystemSolvers.jl:134-136
+            { ProfLaunchScope ps(prof, cat_fwd, lvl); shared_panel<T>(st, SharedPanelOp::forward, a_fwd); }      // :137, L y = t
+            { ProfLaunchScope ps(prof, cat_bwd, lvl); shared_panel<T>(st, SharedPanelOp::backward_x, a_bwd); }   // :137, L' x~ = y; SolveQuadraticProgram.jl:56-57
+            { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, SharedPanelOp::rows_zy, a_row); }     // :139; SolveQuadraticProgram.jl:59-61
+            if (ii % p.numItrConv != 0) continue;                                                   // :63
+            {
+                ProfScope ps(prof, cat_chk, 2);
+                HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long) * (size_t)CP, st));
+                shared_panel<T>(st, SharedPanelOp::product, a_ax);                                  // mA * vX
+                shared_panel<T>(st, SharedPanelOp::product, a_px);                                  // mP * vX
+                shared_panel<T>(st, SharedPanelOp::product, a_aty);                                 // mA' * vY
+                shared_check<T>(st, (int)n, (int)m, NP, MP, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho);   // :64
+            }
+            HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            prof.harvest();
+            bool any_done = false;
+            for (int b = 0; b < count; ++b) {
+                if (!active[b]) continue;
+                const double* r = res_host + 8 * b;
+                resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
+                if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
+            }
+            if (any_done && nactive > 0) push_active();
+        }
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+        const double t2 = now_s();
+        get_panels(x, xh, n, NP);
+        for (int b = 0; b < count && infos; ++b) {
+            qps_info& in = infos[b];
+            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = 0; in.cgIterations = 0;
+            in.rhoFinal = rho; in.rhoProposed = rho; in.resPrim = resP[b]; in.resDual = resD[b];
+            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = 0;   // wall time of the whole batch
+            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
+            in.trsvBlock = nb; in.sweepVariant = 3; in.sweepGaveUp = 0; in.cgExplicit = 0;
         }
     }
 };
@@ -1118,6 +1300,51 @@ QPS_API int32_t qps_solve_batch(qps_handle hh, double* x, const qps_params* p, q
         if (rc != QPS_OK) return rc;
     }
     return QPS_OK;
+}
+
+QPS_API int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda,
+                                              const double* q, const double* l, const double* u, int32_t dtype, int32_t device, qps_handle* out) {
+    if (!out) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "out handle pointer is NULL");
+    *out = nullptr;
+    if (count <= 0 || count > 65535) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "batch count must be in 1..65535");
+    if (n <= 0 || m < 0) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "need n >= 1 and m >= 0");
+    if (n > (1 << 20) || m > (1 << 24)) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "dense problem too large");
+    if (!P || !q || (m > 0 && (!A || !l || !u))) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "NULL problem array");
+    if (ldp < n || (m > 0 && lda < m)) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "leading dimension smaller than the row count");
+    if (dtype != QPS_F64 && dtype != QPS_F32) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "unknown dtype");
+    if (!all_finite_matrix(P, n, n, ldp)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "P contains NaN/Inf");
+    if (m > 0 && !all_finite_matrix(A, m, n, lda)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "A contains NaN/Inf");
+    if (!all_finite(q, count * n, false)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "q contains NaN/Inf");
+    if (m > 0 && (!all_finite(l, count * m, true) || !all_finite(u, count * m, true))) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "l/u contain NaN");
+    {
+        const int64_t bad = dense_asymmetry(P, n, ldp);                              // SolveQuadraticProgram.m:166-168
+        if (bad >= 0) { char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)bad); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b); }
+    }
+    if (m == 0) return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch needs m >= 1 (without constraints the columns are independent linear solves)");
+    if (roundup(n, 64) > (dtype == QPS_F64 ? shared_batch_max_np<double>() : shared_batch_max_np<float>()))
+        return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch: n beyond the limit of the whole-factor explicit inverse (16384 fp64, 32768 fp32)");
+    if (const int dc = require_device(device)) return dc;
+    Handle* h = new Handle(); h->n = n; h->m = m;
+    int rc = guarded(nullptr, [&] {
+        auto load = [&](auto s) { s->load(P, ldp, A, lda, q, l, u); h->fused_batch = s.release(); };   // a unique_ptr: a throw while loading drops the solver
+        if (dtype == QPS_F64) load(std::make_unique<SharedBatchSolver<double>>(device, (int)count, n, m));
+        else load(std::make_unique<SharedBatchSolver<float>>(device, (int)count, n, m));
+    });
+    if (rc != QPS_OK) { delete h; return rc; }
+    *out = reinterpret_cast<qps_handle>(h);
+    return QPS_OK;
+}
+
+QPS_API int32_t qps_update_shared_vectors(qps_handle hh, const double* q, const double* l, const double* u) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h || !h->fused_batch) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "not a shared-matrix batch handle");
+    const int64_t c = h->fused_batch->count;
+    if (q && !all_finite(q, c * h->n, false)) return fail_with(h, QPS_ERR_NOT_FINITE, "q contains NaN/Inf");
+    if ((l && !all_finite(l, c * h->m, true)) || (u && !all_finite(u, c * h->m, true))) return fail_with(h, QPS_ERR_NOT_FINITE, "l/u contain NaN");
+    bool shared = false;
+    const int rc = guarded(h, [&] { shared = h->fused_batch->update_vectors(q, l, u); });
+    if (rc != QPS_OK) return rc;
+    return shared ? QPS_OK : fail_with(h, QPS_ERR_BAD_ARGUMENT, "not a shared-matrix batch handle");
 }
 
 QPS_API int32_t qps_solve_batch_multi(int64_t count, int64_t n, int64_t m, const double* P, const double* A, const double* q, const double* l, const double* u,

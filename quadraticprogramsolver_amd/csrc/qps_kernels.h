@@ -118,6 +118,41 @@ template <typename T> int sweep_fused_slabs(int NP, int count = 1);
 template <typename T>
 int sweep_fused(hipStream_t st, const T* S, int64_t ld, int NP, const T* v, T* part, int64_t part_ld, BatchStride bs = BatchStride());
 
+// ---- shared-matrix batch (k_shared.hip): many QPs on ONE P and ONE A, state in 16-column panels ------------------------------
+// A length-R vector of `count` QPs is stored as panels [panel][rowsP][16]: QP b = column b % 16 of panel b / 16, rowsP = NP or MP, the column
+// count padded to a multiple of 16 with columns that stay zero and inactive.  Every product of the loop is
+//     out[panel][r][16] = sum_k Mat[r][k] * B[panel][k][16]          Mat row-major (ld), rows and K multiples of 64
+// on the MFMA pipe (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32), the matrix streamed once for all panels of a launch (two panels per
+// workgroup; more panels than that stream it once per pair, the pairs of one row tile side by side on one XCD), with the row-wise part of the
+// iteration as its epilogue.
+template <typename T> struct PanelArgs {
+    const T* Mat = nullptr; int64_t ld = 0; int rows = 0, K = 0;
+    const T* B = nullptr; int npanel = 0;
+    T* out = nullptr;
+    const T* q = nullptr; T *x = nullptr, *xp = nullptr;                                             // rhs, backward_x
+    T *z = nullptr, *zp = nullptr, *y = nullptr, *w = nullptr; const T *l = nullptr, *u = nullptr;   // rows_zy
+    const int* active = nullptr;                                                                     // one word per column (npanel * 16)
+    T alpha = T(0), rho = T(1), sigma = T(0);
+};
+enum class SharedPanelOp {
+    product,      // out = Mat B                                                     (the check's A x, P x, A'y)
+    rhs,          // out = sigma x - q + Mat B                                       LinearSystemSolvers.jl:134-136 with Mat = A', B = rho z - y
+    forward,      // out = tril(Mat) B                                               forward sweep over the sweep matrix S (one inverted block)
+    backward_x,   // out = triu(Mat) B; active columns: xp = x, x = alpha out + (1 - alpha) x      backward sweep + SolveQuadraticProgram.jl:56-57
+    rows_zy       // s = Mat B = z~; active columns: zp = z, z, y updated, w = rho z - y           SolveQuadraticProgram.jl:59-61
+};
+template <typename T> void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a);
+bool shared_panel_small(int rows, int K, size_t elem);   // matrix small enough to stay cached: one panel and 16 waves per workgroup
+// CheckConvergence per column (SolveQuadraticProgram.jl:79-112) on panels: slots = 16 u64 per column (zero-filled by the caller), res_dev = 8 doubles
+// per column laid out as check_convergence's ([4] = rho: the shared batch runs a fixed rho)
+template <typename T>
+void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* Ax, const T* Px, const T* Aty, const T* q, const T* x, const T* xp,
+                  const T* z, const T* zp, unsigned long long* slots, double* res_dev, const int* active, double epsAbs, double epsRel, double epsAdmm,
+                  double rho);
+template <typename T> void to_panels(hipStream_t st, const double* src, int count, int len, int rowsP, T* dst);     // [count][len] doubles -> panels
+template <typename T> void from_panels(hipStream_t st, const T* src, int count, int len, int rowsP, double* dst);   // panels -> [count][len] doubles
+template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int64_t lds, int rows, int cols, T* dst, int64_t ldd);   // dims multiples of 32
+
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);
 template <typename T> void transpose_small(hipStream_t st, const T* A, int NP, int MP, T* At);

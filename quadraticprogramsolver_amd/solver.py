@@ -70,7 +70,39 @@ def _validate_dims(numElementsX, mP, vQ, mA, vL, vU):
         raise ValueError("The vectors vL, vU dimensions must match the rows of mA")
 
 
-class QuadraticProgram:
+class _Handle:
+    """What every wrapper of a qps_handle shares: profiling, destruction, context-manager use."""
+    _h = None
+
+    def set_profiling(self, level: int):
+        _lib.check(_lib.lib().qps_set_profiling(self._h, int(level)), self._h)
+
+    def kernel_times(self):
+        buf = (_lib.QpsKernelTime * 32)()
+        cnt = C.c_int32(0)
+        _lib.check(_lib.lib().qps_kernel_times(self._h, buf, 32, C.byref(cnt)), self._h)
+        return [dict(name=buf[i].name.decode(), seconds=buf[i].seconds, launches=buf[i].launches, algo_bytes=buf[i].algo_bytes)
+                for i in range(cnt.value)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().qps_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class QuadraticProgram(_Handle):
     """A problem resident in HBM (qps_create_dense / qps_create_csc ... qps_destroy).
 
     ``linsys``: "cholesky" (dense reduced form; sparse inputs are densified on the device), "cg" (CSR; CG on the reduced operator: matrix-free
@@ -174,35 +206,8 @@ class QuadraticProgram:
         return out[:{"P": self.n, "A": self.m, "At": self.n, "PA": self.n + self.m, "reduced": self.n}[op]]
 
     # -- profiling ----------------------------------------------------------------------------------------------------
-    def set_profiling(self, level: int):
-        _lib.check(_lib.lib().qps_set_profiling(self._h, int(level)), self._h)
 
-    def kernel_times(self):
-        buf = (_lib.QpsKernelTime * 32)()
-        cnt = C.c_int32(0)
-        _lib.check(_lib.lib().qps_kernel_times(self._h, buf, 32, C.byref(cnt)), self._h)
-        return [dict(name=buf[i].name.decode(), seconds=buf[i].seconds, launches=buf[i].launches, algo_bytes=buf[i].algo_bytes)
-                for i in range(cnt.value)]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().qps_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class QuadraticProgramBatch:
+class QuadraticProgramBatch(_Handle):
     """A batch of independent dense QPs of one shape resident in HBM (qps_create_dense_batch / qps_solve_batch):
     the per-problem loop of RunBenchmarks.jl:88-104 advanced in lock step by batched launches.  Every QP keeps its own
     rho, proposed rho, convergence flag and stopping iteration, exactly as if solved alone."""
@@ -274,22 +279,68 @@ class QuadraticProgramBatch:
             _lib.check(_lib.lib().qps_get_dual(self._h, _dp(Z), _dp(Y)), self._h)
         return Z[:, :self.m], Y[:, :self.m]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().qps_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class QuadraticProgramSharedBatch(_Handle):
+    """``count`` QPs on ONE ``mP`` and ONE ``mA`` that differ in ``q``, ``l`` and ``u`` only (qps_create_dense_shared_batch): an MPC horizon
+    re-solved every sample, a regularisation path, a scenario sweep.  ``mQ`` is [count x n], ``mL`` / ``mU`` are [count x m].  The matrices are
+    stored, factorised and streamed once for all columns; every column keeps its own check, flag, stopping iteration and residuals, exactly as if
+    solved alone with a fixed ρ (``adptΡ``, ``polish`` and a ``trsvBlock`` below n are refused with QPS_ERR_UNSUPPORTED)."""
 
-    def __enter__(self):
-        return self
+    def __init__(self, mP, mA, mQ, mL, mU, *, dtype="f64", device=0):
+        dense = lambda M: np.asarray(M.toarray() if sp.issparse(M) else M, dtype=np.float64)
+        mP, mA = dense(mP), dense(mA)
+        if mP.ndim != 2 or mA.ndim != 2:
+            raise ValueError("mP and mA must be matrices")
+        self.n, self.m = mP.shape[0], mA.shape[0]
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(mQ, dtype=np.float64)))
+        self.count = q.shape[0]
+        l, u = self._rows(mL, "mL", self.m), self._rows(mU, "mU", self.m)
+        for b in range(self.count):
+            _validate_dims(self.n, mP, q[b], mA, l[b], u[b])
+        Pd, Ad = np.asfortranarray(mP), np.asfortranarray(mA)
+        h = C.c_void_p()
+        dt = {"f64": QPS_F64, "f32": QPS_F32}[dtype]
+        _lib.check(_lib.lib().qps_create_dense_shared_batch(self.count, self.n, self.m, _dp(Pd), max(self.n, 1), _dp(Ad), max(self.m, 1),
+                                                            _dp(q), _dp(l), _dp(u), dt, device, C.byref(h)))
+        self._h = h
 
-    def __exit__(self, *a):
-        self.close()
+    def _rows(self, M, name, length):
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(M, dtype=np.float64)))
+        if a.shape != (self.count, length):
+            raise ValueError(f"dimension mismatch: {name} has shape {a.shape}, expected {(self.count, length)}")
+        return a
+
+    def update(self, mQ=None, mL=None, mU=None):
+        """Replaces q, l and / or u of every column (``None`` keeps the array).  The factorisation does not depend on them: a following
+        ``solve(reuseFactor=True)`` with unchanged (ρ, σ) does not factorise again."""
+        q = None if mQ is None else self._rows(mQ, "mQ", self.n)
+        l = None if mL is None else self._rows(mL, "mL", self.m)
+        u = None if mU is None else self._rows(mU, "mU", self.m)
+        ptr = lambda a: None if a is None else _dp(a)
+        _lib.check(_lib.lib().qps_update_shared_vectors(self._h, ptr(q), ptr(l), ptr(u)), self._h)
+
+    def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
+              trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
+        """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts), as ``QuadraticProgramBatch.solve``.  ``mX`` (optional) holds the warm starts."""
+        X = np.zeros((self.count, self.n)) if mX is None else np.ascontiguousarray(mX, dtype=np.float64).copy()
+        if X.shape != (self.count, self.n):
+            raise ValueError(f"dimension mismatch: mX has shape {X.shape}, expected {(self.count, self.n)}")
+        p = _lib.default_params()
+        p.numIterations, p.epsAbs, p.epsRel = int(numIterations), float(ϵAbs), float(ϵRel)
+        p.rho, p.sigma, p.alpha = float(ρ), float(σ), float(α)
+        p.adptRho, p.fctrRho, p.numItrConv = int(bool(adptΡ)), float(fctrΡ), int(numItrConv)
+        p.trsvBlock, p.reuseFactor = int(trsvBlock), int(bool(reuseFactor))
+        p.polish, p.numItrPolish, p.delta, p.epsMinres, p.numItrMinres = int(bool(polish)), int(numItrPolish), float(δ), float(ϵMinres), int(numItrMinres)
+        infos = (QpsInfo * self.count)()
+        _lib.check(_lib.lib().qps_solve_batch(self._h, _dp(X), C.byref(p), infos), self._h)
+        return X, [ConvergenceFlag(i.convFlag) for i in infos], [i.as_dict() for i in infos]
+
+    def dual(self):
+        """(mZ, mY) [count x m] of the last solve (additive: the reference discards them)."""
+        Z = np.zeros((self.count, self.m))
+        Y = np.zeros((self.count, self.m))
+        _lib.check(_lib.lib().qps_get_dual(self._h, _dp(Z), _dp(Y)), self._h)
+        return Z, Y
 
 
 # ------------------------------------------------------------------------------------------------------------------
