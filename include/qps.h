@@ -229,6 +229,25 @@ int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t m, const
                                       const double *q, const double *l, const double *u, int32_t dtype, int32_t device, qps_handle *out);
 int32_t qps_update_shared_vectors(qps_handle h, const double *q, const double *l, const double *u);
 
+/* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
+ * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
+ * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads
+ * them at its first direct solve), one numeric factorisation serves every column, and every iteration sweeps 16 columns per launch.
+ * Matrices are validated as by qps_create_csc, the vectors as by qps_create_dense_shared_batch for every column, before a device is needed; count <= 65535.
+ * QPS_ERR_UNSUPPORTED from the create call: m = 0, or a pattern the level-scheduled plugin refuses (the analysis' message; still before a device is needed).
+ * The handle is a batch handle like the dense one: qps_solve_batch, qps_get_dual, qps_update_shared_vectors, qps_set_profiling, qps_kernel_times,
+ * qps_last_error and qps_destroy work on it, and column b behaves as a stand-alone qps_solve on a CSC handle with QPS_LINSYS_KKT_LDL and a fixed rho: its own
+ * check, flag, iteration count and residuals; x, z, y are the iterates of its own stopping iteration.  A column of a batch equals the same data in a batch of
+ * one bit for bit.
+ * qps_solve_batch refuses with QPS_ERR_UNSUPPORTED (the handle stays usable): adptRho != 0, polish != 0, a linsys other than QPS_LINSYS_AUTO or
+ * QPS_LINSYS_KKT_LDL.  trsvBlock and loopVariant are accepted and without effect (they steer dense sweeps).  With reuseFactor = 1 and unchanged (rho, sigma)
+ * nothing is factorised again, also after qps_update_shared_vectors.  qps_info per column: sweepVariant = 0, trsvBlock = 0, numRefactor = 0.
+ * Environment, read once per handle at creation: QPS_LDL_PANEL_SPR = 1 | 4 | 16 forces that many 16-lane strips per factor row in every level of the sweeps
+ * (unset: chosen per level from the mean row length). */
+int32_t qps_create_csc_shared_batch(int64_t count, int64_t n, int64_t m, const int64_t *P_colptr, const int64_t *P_rowval, const double *P_nzval,
+                                    const int64_t *A_colptr, const int64_t *A_rowval, const double *A_nzval, const double *q, const double *l,
+                                    const double *u, int32_t index_base, int32_t dtype, int32_t device, qps_handle *out);
+
 /* The per-problem loop of RunBenchmarks.jl:88-104 sharded over the devices of ONE process ("one host thread + one stream per device", "work-stealing at
  * chunk boundaries").  `count` independent dense QPs of one shape, arrays stacked as for qps_create_dense_batch; `devices[num_workers]` lists the device of every worker
  * -- one host thread each; a device may be listed more than once (two workers sharing a card).  Every worker repeatedly takes the next range of QPs from a shared

@@ -366,6 +366,24 @@ function SharedBatchCreate(mP::Matrix{Float64}, mQ::Matrix{Float64}, mA::Matrix{
     return SharedBatchHip(h[], n, m, count)
 end
 
+# The same family on a SPARSE mP and mA (qps_create_csc_shared_batch): the sparse L D L' of the KKT matrix is analysed once at creation and factorised once
+# for all columns, every iteration sweeps 16 columns per launch.  The handle is a SharedBatchHip: SharedBatchUpdate! / SharedBatchSolve! / SharedBatchDestroy
+# work on it unchanged (adptΡ is refused by the library; a column behaves as the FacLdl / QDLdl / LaLdl plugin with a fixed ρ).
+function SharedBatchCreate(mP::SparseMatrixCSC{Float64, Int64}, mQ::Matrix{Float64}, mA::SparseMatrixCSC{Float64, Int64}, mL::Matrix{Float64}, mU::Matrix{Float64};
+    device = 0, dtype::Type = Float64)
+    n = size(mP, 1); m = size(mA, 1); count = size(mQ, 2)
+    size(mP, 2) == n || throw(DimensionMismatch("The matrix mP must be square"))
+    size(mA, 2) == n || throw(DimensionMismatch("The number of columns of mA must match mP"))
+    size(mQ, 1) == n || throw(DimensionMismatch("mQ must be n x count"))
+    (size(mL) == (m, count) && size(mU) == (m, count)) || throw(DimensionMismatch("mL and mU must be m x count"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mP mA mQ mL mU _check(ccall((:qps_create_csc_shared_batch, LIBQPS), Int32,
+        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+        count, n, m, mP.colptr, mP.rowval, mP.nzval, mA.colptr, mA.rowval, mA.nzval, mQ, mL, mU, Int32(1), _dtype(dtype), Int32(device), h))   # index_base = 1
+    return SharedBatchHip(h[], n, m, count)
+end
+
 function SharedBatchUpdate!(sb::SharedBatchHip; mQ::Union{Nothing, Matrix{Float64}} = nothing, mL::Union{Nothing, Matrix{Float64}} = nothing,
     mU::Union{Nothing, Matrix{Float64}} = nothing)
     h = sb.h

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "qps_kernels.h"
+#include "panel_strips.h"
 #include "qps_ldl.h"
 #include "wave_reduce.h"
 
@@ -236,6 +237,92 @@ __global__ __launch_bounds__(256) void k_ldl_post_update(int n, int m, int Ns, c
     }
 }
 
+// ---- panel forms of the per-iteration kernels (shared-matrix batch) --------------------------------------------------------
+// b is [panel][N][16] in permuted order, tb / tu / tx are [panel][ldt][16], the ADMM state [panel][n][16] / [panel][m][16]; lane % 16 is the QP column and
+// blockIdx.y the panel.  The arithmetic per column is that of the scalar kernels above.  A column whose active word is 0 keeps its state; its right-hand side is
+// set to zero so that the sweeps carry zeros for it (nothing of a stopped column's result reads b).
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_rhs_panel(int N, int n, int m, const int* __restrict__ perm, const T* __restrict__ x, const T* __restrict__ q,
+                                                       const T* __restrict__ z, const T* __restrict__ y, const int* __restrict__ active, T sigma, T rho1,
+                                                       T* __restrict__ b) {
+    const int e = blockIdx.x * 256 + threadIdx.x, k = e >> 4, col = e & 15, P = blockIdx.y;
+    if (k >= N) return;
+    const int o = perm[k];
+    T v = T(0);
+    if (active[P * 16 + col]) {
+        if (o < n) { const int64_t i = ((int64_t)P * n + o) * 16 + col; v = sigma * x[i] - q[i]; }                      // LinearSystemSolvers.jl:37
+        else { const int64_t i = ((int64_t)P * m + (o - n)) * 16 + col; v = z[i] - rho1 * y[i]; }                       // :38
+    }
+    b[((int64_t)P * N + k) * 16 + col] = v;
+}
+// forward substitution for the rows [r0, r1) of one level (or of the tail), one (row, panel) per 16 SPR lanes
+template <typename T, int SPR>
+__global__ __launch_bounds__(PS_THREADS) void k_ldl_fwd_panel(int r0, int r1, int N, int Ns, int ldt, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                               const T* __restrict__ vr, T* __restrict__ b, T* __restrict__ tb) {
+    const int r = r0 + blockIdx.x * (PS_THREADS / (16 * SPR)) + threadIdx.x / (16 * SPR), strip = (threadIdx.x >> 4) % SPR, col = threadIdx.x & 15;
+    const bool valid = r < r1;
+    T* bp = b + (int64_t)blockIdx.y * N * 16 + col;
+    T s = T(0);
+    if (valid) s = strip_dot<T, SPR>(rp[r], rp[r + 1], strip, ci, vr, [&](int i) { return bp[(int64_t)i * 16]; });
+    s = strips_sum<T, SPR>(s);
+    if (valid && strip == 0) {
+        const T v = bp[(int64_t)r * 16] - s;
+        if (r >= Ns) tb[((int64_t)blockIdx.y * ldt + (r - Ns)) * 16 + col] = v; else bp[(int64_t)r * 16] = v;
+    }
+}
+// backward substitution for the columns [c0, c1) of one level
+template <typename T, int SPR>
+__global__ __launch_bounds__(PS_THREADS) void k_ldl_bwd_panel(int c0, int c1, int N, int Ns, int ldt, const int* __restrict__ cp, const int* __restrict__ ri,
+                                                               const T* __restrict__ vc, const T* __restrict__ Dinv, T* __restrict__ b, const T* __restrict__ tx) {
+    const int j = c0 + blockIdx.x * (PS_THREADS / (16 * SPR)) + threadIdx.x / (16 * SPR), strip = (threadIdx.x >> 4) % SPR, col = threadIdx.x & 15;
+    const bool valid = j < c1;
+    T* bp = b + (int64_t)blockIdx.y * N * 16 + col;
+    const T* tp = tx + (int64_t)blockIdx.y * ldt * 16 + col;
+    T s = T(0);
+    if (valid) s = strip_dot<T, SPR>(cp[j], cp[j + 1], strip, ri, vc, [&](int i) { return i >= Ns ? tp[(int64_t)(i - Ns) * 16] : bp[(int64_t)i * 16]; });
+    s = strips_sum<T, SPR>(s);
+    if (valid && strip == 0) bp[(int64_t)j * 16] = bp[(int64_t)j * 16] * Dinv[j] - s;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_mul_sign_panel(int ldt, const T* __restrict__ sgn, T* __restrict__ u) {
+    const int e = blockIdx.x * 256 + threadIdx.x, i = e >> 4;
+    if (i < ldt && sgn[i] < T(0)) { const int64_t a = (int64_t)blockIdx.y * ldt * 16 + e; u[a] = -u[a]; }
+}
+// k_ldl_post_update per column: thread (o, col) owns entry o of [x; nu] of one column
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_post_update_panel(int n, int m, int N, int Ns, int ldt, const int* __restrict__ iperm, T* __restrict__ b,
+                                                               const T* __restrict__ tx, const T* __restrict__ q, T* __restrict__ x, T* __restrict__ xp,
+                                                               T* __restrict__ z, T* __restrict__ zp, T* __restrict__ y, const T* __restrict__ l,
+                                                               const T* __restrict__ u, const int* __restrict__ active, T alpha, T rho, T sigma) {
+    const int e = blockIdx.x * 256 + threadIdx.x, o = e >> 4, col = e & 15, P = blockIdx.y;
+    if (o >= n + m) return;
+    const int k = iperm[o];
+    const int64_t bi = ((int64_t)P * N + k) * 16 + col;
+    if (!active[P * 16 + col]) { b[bi] = T(0); return; }
+    const T v = k >= Ns ? tx[((int64_t)P * ldt + (k - Ns)) * 16 + col] : b[bi];       // every thread reads its own b entry before it overwrites it
+    const T alpha1 = T(1) - alpha, rho1 = T(1) / rho;
+    if (o < n) {
+        const int64_t i = ((int64_t)P * n + o) * 16 + col;
+        const T xo = x[i];
+        xp[i] = xo;                                                           // :56
+        const T xn = alpha * v + alpha1 * xo;                                 // :57
+        x[i] = xn;
+        b[bi] = sigma * xn - q[i];                                            // next :37
+    } else {
+        const int64_t i = ((int64_t)P * m + (o - n)) * 16 + col;
+        const T zo = z[i], yo = y[i];
+        const T zt = zo + rho1 * (v - yo);                                    // LinearSystemSolvers.jl:40  nu -> z~
+        zp[i] = zo;                                                           // :59
+        const T t = alpha * zt + alpha1 * zo + rho1 * yo;                     // :60
+        const T lo = l[i], hi = u[i];
+        const T zn = t > hi ? hi : (t < lo ? lo : t);
+        z[i] = zn;
+        const T yn = yo + rho * (alpha * zt + alpha1 * zo - zn);              // :61
+        y[i] = yn;
+        b[bi] = zn - rho1 * yn;                                               // next :38
+    }
+}
+
 // ---- dense signed Cholesky of the tail (one 64-column step = diagonal block, panel, MFMA trailing update) -----------------
 // 64 x 64 block: M = Lt J Lt' with J = diag(sgn).  Column k: d = sgn_k a_kk > 0, Lt_kk = sqrt(d), Lt_ik = sgn_k a_ik / sqrt(d);
 // trailing a_ij -= Lt_ik sgn_k Lt_jk.  The inverse of Lt (lower) follows by forward substitution on the identity.
@@ -318,6 +405,7 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
     std::vector<int> group_ptr; int KC = 16, GS = 1, nb = 64; bool tail_signed = false;   // Schur complement: groups of GS K-slices of KC columns
     DevVec<T> slabs;
     std::vector<int> lpr_fwd, lpr_bwd; int lpr_tail = 1;
+    DevVec<T> bP, tbP, tuP, txP; int npanel = 0; std::vector<int> spr_fwd, spr_bwd; int spr_tail = 1;   // panel forms (panels_prepare)
 
     SparseLdlImpl(hipStream_t st_, LdlSymbolic&& sym, const double* Pv, int64_t pnnz, const double* Av, int64_t annz) : st(st_), S(std::move(sym)) {
         const int N = S.N, Ns = S.Ns, Nt = S.Nt, ldt = S.ldt;
@@ -459,6 +547,68 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
         sweeps();
         hipLaunchKernelGGL((k_ldl_post_update<T>), dim3((N + 255) / 256), dim3(256), 0, st, S.n, S.m, S.Ns, iperm.p, b.p, tx.p, q, x, xp, z, zp, y, l, u,
                            (T)alpha, (T)rho, (T)sigma);
+    }
+    // ---- panel forms ----
+    void panels_prepare(int npanel_, int spr) override {
+        const int N = S.N, Ns = S.Ns, Nt = S.Nt, ldt = S.ldt, L = (int)S.level_ptr.size() - 1;
+        npanel = npanel_;
+        bP.alloc((int64_t)npanel * N * 16, st);
+        const int64_t tl = (int64_t)npanel * std::max(ldt, 4) * 16;
+        tbP.alloc(tl, st); tuP.alloc(tl, st); txP.alloc(tl, st);   // zero-filled: the padding rows [Nt, ldt) of tb are never written and stay zero
+        spr_fwd.assign(std::max(L, 0), 1); spr_bwd.assign(std::max(L, 0), 1);
+        const bool forced = spr == 1 || spr == 4 || spr == 16;
+        for (int l = 0; l < L; ++l) {
+            const int c0 = S.level_ptr[l], c1 = S.level_ptr[l + 1];
+            spr_fwd[l] = forced ? spr : pick_panel_spr((int64_t)S.rp[c1] - S.rp[c0], c1 - c0);
+            spr_bwd[l] = forced ? spr : pick_panel_spr((int64_t)S.cp[c1] - S.cp[c0], c1 - c0);
+        }
+        spr_tail = forced ? spr : pick_panel_spr((int64_t)S.rp[N] - S.rp[Ns], Nt);
+    }
+    int panel_launches_per_solve() const override { return launches_per_solve(); }
+    template <int SPR> void fwd_panel_launch(int r0, int r1) {
+        constexpr int RPB = PS_THREADS / (16 * SPR);
+        hipLaunchKernelGGL((k_ldl_fwd_panel<T, SPR>), dim3((unsigned)((r1 - r0 + RPB - 1) / RPB), (unsigned)npanel), dim3(PS_THREADS), 0, st, r0, r1, S.N, S.Ns, S.ldt,
+                           rp.p, ci.p, vr.p, bP.p, tbP.p);
+    }
+    void fwd_panel(int r0, int r1, int spr) { if (r1 <= r0) return; if (spr == 1) fwd_panel_launch<1>(r0, r1); else if (spr == 4) fwd_panel_launch<4>(r0, r1); else fwd_panel_launch<16>(r0, r1); }
+    template <int SPR> void bwd_panel_launch(int c0, int c1) {
+        constexpr int RPB = PS_THREADS / (16 * SPR);
+        hipLaunchKernelGGL((k_ldl_bwd_panel<T, SPR>), dim3((unsigned)((c1 - c0 + RPB - 1) / RPB), (unsigned)npanel), dim3(PS_THREADS), 0, st, c0, c1, S.N, S.Ns, S.ldt,
+                           cp.p, ri.p, vc.p, Dinv.p, bP.p, txP.p);
+    }
+    void bwd_panel(int c0, int c1, int spr) { if (c1 <= c0) return; if (spr == 1) bwd_panel_launch<1>(c0, c1); else if (spr == 4) bwd_panel_launch<4>(c0, c1); else bwd_panel_launch<16>(c0, c1); }
+    void iterate_panels(const LdlPanelState<T>& s, double alpha, double rho, double sigma, bool rhs_ready, const LdlPanelProf& pf) override {
+        const int N = S.N, Ns = S.Ns, Nt = S.Nt, ldt = S.ldt, L = (int)S.level_ptr.size() - 1;
+        if (s.npanel != npanel) throw QpsError(QPS_ERR_BAD_ARGUMENT, "iterate_panels: panel count differs from panels_prepare");
+        Profiler none; Profiler& pr = pf.prof ? *pf.prof : none;   // (level 0: its scopes record nothing)
+        const dim3 gN((unsigned)(((int64_t)N * 16 + 255) / 256), (unsigned)npanel);
+        if (!rhs_ready) {
+            ProfScope ps(pr, pf.cat_rhs, pf.lvl);
+            hipLaunchKernelGGL((k_ldl_rhs_panel<T>), gN, dim3(256), 0, st, N, S.n, S.m, perm.p, s.x, s.q, s.z, s.y, s.active, (T)sigma, (T)(1.0 / rho), bP.p);
+        }
+        {
+            ProfScope ps(pr, pf.cat_fwd, pf.lvl);
+            for (int l = 1; l < L; ++l) fwd_panel(S.level_ptr[l], S.level_ptr[l + 1], spr_fwd[l]);   // level 0: leaves, nothing to subtract
+            if (Nt > 0) fwd_panel(Ns, N, spr_tail);                                                   // tb = b_t - L_ts y_s
+        }
+        if (Nt > 0) {
+            ProfScope ps(pr, pf.cat_tail, pf.lvl);
+            PanelArgs<T> a; a.Mat = St.p; a.ld = ldt; a.rows = ldt; a.K = ldt; a.npanel = npanel; a.active = s.active;
+            a.B = tbP.p; a.out = tuP.p;
+            shared_panel<T>(st, SharedPanelOp::forward, a);                                          // inv(Lt) tb
+            if (tail_signed) hipLaunchKernelGGL((k_ldl_mul_sign_panel<T>), dim3((ldt * 16 + 255) / 256, (unsigned)npanel), dim3(256), 0, st, ldt, tsgn.p, tuP.p);   // J .
+            a.B = tuP.p; a.out = txP.p;
+            shared_panel<T>(st, SharedPanelOp::backward, a);                                         // inv(Lt)' .
+        }
+        {
+            ProfScope ps(pr, pf.cat_bwd, pf.lvl);
+            for (int l = L - 1; l >= 0; --l) bwd_panel(S.level_ptr[l], S.level_ptr[l + 1], spr_bwd[l]);
+        }
+        {
+            ProfScope ps(pr, pf.cat_post, pf.lvl);
+            hipLaunchKernelGGL((k_ldl_post_update_panel<T>), gN, dim3(256), 0, st, S.n, S.m, N, Ns, ldt, iperm.p, bP.p, txP.p, s.q, s.x, s.xp, s.z, s.zp, s.y, s.l, s.u,
+                               s.active, (T)alpha, (T)rho, (T)sigma);
+        }
     }
     void solve_raw(const T* r1, const T* r2, T* out_x, T* out_nu) override {
         const int N = S.N;

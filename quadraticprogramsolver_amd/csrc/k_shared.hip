@@ -328,6 +328,7 @@ void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a) {
         case SharedPanelOp::product: panel_shape<T, 0, 0>(st, a); break;
         case SharedPanelOp::rhs: panel_shape<T, 0, 1>(st, a); break;
         case SharedPanelOp::forward: panel_shape<T, 1, 0>(st, a); break;
+        case SharedPanelOp::backward: panel_shape<T, 2, 0>(st, a); break;
         case SharedPanelOp::backward_x: panel_shape<T, 2, 2>(st, a); break;
         case SharedPanelOp::rows_zy: panel_shape<T, 0, 3>(st, a); break;
     }

@@ -13,6 +13,7 @@
 #include "qps_internal.h"
 #include "spmv_layout.h"
 #include "qps_kernels.h"
+#include "qps_ldl.h"
 #include "qps_polish.h"
 #include "qps_proxqp.h"
 
@@ -977,6 +978,170 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
 };
 
 // =================================================================================================================
+// Sparse shared-matrix batch: `count` QPs on ONE sparse P and ONE sparse A (a lasso / SVM regularisation path, a scenario sweep on a sparse model).
+// The linear system is the sparse L D L' of the KKT matrix (k_ldl.hip): ordering and symbolic factor once at creation (host only), ONE numeric
+// factorisation per (rho, sigma), and every iteration runs the level-scheduled sweeps on 16-column panels -- the index and value of a factor entry are
+// loaded once for 16 QPs, the launch chain is paid once per batch.  The check's A x, P x, A'y are CSR x panel products (k_csr_panel.hip).
+// rho is fixed; every column keeps its own check, flag, stopping iteration and residuals and is frozen by the active mask, as in SharedBatchSolver.
+// =================================================================================================================
+struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
+    LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;
+};
+template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
+    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
+    int CP = 0, npanel = 0;
+    std::unique_ptr<SparseLdl<T>> ldl;
+    CsrPanelMatrix<T> P, A, At;
+    T *q = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *xp = nullptr, *z = nullptr, *zp = nullptr, *y = nullptr, *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
+    int* d_active = nullptr; int* h_int = nullptr;
+    unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
+    bool factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
+    LdlPanelProf pf; int cat_chk = 0;
+    std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
+
+    SparseSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, SparseSharedInput&& in, const double* qh, const double* lh, const double* uh) {
+        device = dev; n = n_; m = m_; count = cnt;
+        HIPC(hipSetDevice(device));
+        st = prof.st = lease.acquire(device);
+        CP = roundup(count, 16); npanel = CP / 16;
+        up.reset(new StagedUploader(st));
+        layout::CsrHost Ph, Ah, Ath;
+        try {
+            Ph = layout::csc_as_transposed_csr(n, n, in.Pcp, in.Pri, in.Pnz);      // P: CSC == CSR (symmetric, full storage)
+            layout::csc_to_csr_pair(m, n, in.Acp, in.Ari, in.Anz, Ah, Ath);        // rows of A by a counting sort; rows of A' are the columns of A
+        } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
+        P = upload_csr(Ph); A = upload_csr(Ah); At = upload_csr(Ath);
+        const int64_t pnnz = (int64_t)in.Pnz.size(), annz = (int64_t)in.Anz.size();
+        const int64_t nnzL = (int64_t)in.sym.ci.size(); const int N = in.sym.N, Ns = in.sym.Ns, ldt = in.sym.ldt;
+        ldl = make_sparse_ldl<T>(st, std::move(in.sym), in.Pnz.data(), pnnz, in.Anz.data(), annz);
+        ldl->panels_prepare(npanel, in.spr);
+        const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
+        q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
+        l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
+        d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
+        slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
+        stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
+        // algorithmic bytes per iteration (check: per check), counted as SparseLdl::bytes_per_solve does: every factor entry's index and value once per panel,
+        // the lines it gathers and the vectors read and written once per column
+        const double s = sizeof(T), c = CP, np = npanel, Nd = N, ents = (double)nnzL;
+        pf.prof = &prof;
+        pf.cat_rhs = prof.category("sparse shared: rhs (panels)", 4.0 * Nd * np + s * c * (2.0 * n + 2.0 * m + Nd));
+        pf.cat_fwd = prof.category("sparse shared: forward levels (panels)", np * ents * (s + 4) + s * c * (ents + 2.0 * Nd));
+        pf.cat_tail = prof.category("sparse shared: dense tail (MFMA panels)", s * ((double)ldt * (ldt + 1) + 6.0 * c * ldt));
+        pf.cat_bwd = prof.category("sparse shared: backward levels (panels)", np * ents * (s + 4) + s * c * (ents + 3.0 * Ns));
+        pf.cat_post = prof.category("sparse shared: post + update (panels)", 4.0 * Nd * np + s * c * (2.0 * Nd + 5.0 * n + 8.0 * m));
+        cat_chk = prof.category("sparse shared: check (A x, P x, A'y, norms)", np * (2.0 * annz + pnnz) * (s + 4) + s * c * ((2.0 * annz + pnnz) + 8.0 * n + 6.0 * m));
+        update_vectors(qh, lh, uh);
+    }
+    ~SparseSharedBatchSolver() override {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(st);
+        prof.release_events();
+    }
+    CsrPanelMatrix<T> upload_csr(const layout::CsrHost& h) {
+        CsrPanelMatrix<T> M; M.rows = h.nrows;
+        int* rp = mem.dalloc<int>((int64_t)h.rp.size(), st); int* ci = mem.dalloc<int>((int64_t)h.ci.size(), st); T* va = mem.dalloc<T>((int64_t)h.va.size(), st);
+        std::vector<T> v(h.va.begin(), h.va.end());
+        up->copy(rp, h.rp.data(), sizeof(int) * h.rp.size());
+        if (!h.ci.empty()) { up->copy(ci, h.ci.data(), sizeof(int) * h.ci.size()); up->copy(va, v.data(), sizeof(T) * v.size()); }
+        M.rp = rp; M.ci = ci; M.va = va; M.spr = csr_panel_spr((int64_t)h.ci.size(), h.nrows);
+        return M;
+    }
+    // host [count][len] doubles -> panels (padding columns zero); ordered on the stream, the host array is free when this returns
+    void put_panels(const double* h, T* d, int64_t len) {
+        HIPC(hipMemsetAsync(d, 0, sizeof(T) * (size_t)CP * (size_t)len, st));
+        up->copy(stage, h, sizeof(double) * (size_t)count * (size_t)len);
+        to_panels<T>(st, stage, count, (int)len, (int)len, d);
+        HIPC(hipStreamSynchronize(st));
+    }
+    void get_panels(const T* d, double* h, int64_t len) {
+        from_panels<T>(st, d, count, (int)len, (int)len, stage);
+        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count * (size_t)len, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    bool update_vectors(const double* qh, const double* lh, const double* uh) override {
+        HIPC(hipSetDevice(device));
+        if (qh) put_panels(qh, q, n);
+        if (lh) put_panels(lh, l, m);
+        if (uh) put_panels(uh, u, m);
+        return true;   // the factor depends on P, A, rho, sigma only: it stays valid
+    }
+    void get_dual(double* zh, double* yh) override {
+        HIPC(hipSetDevice(device));
+        if (zh) get_panels(z, zh, m);
+        if (yh) get_panels(y, yh, m);
+    }
+    void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
+        HIPC(hipSetDevice(device));
+        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: adptRho is not supported (one factor serves every column, so rho is common and fixed)");
+        if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: polish is not supported");
+        if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_KKT_LDL) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: linsys must be QPS_LINSYS_AUTO or QPS_LINSYS_KKT_LDL");
+        const double t0 = now_s();
+        const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
+        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
+        const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
+        if (!reuse) {                                                                               // :36: numeric factorisation, once for all columns
+            factor_valid = false;
+            ++num_factorizations;
+            ldl->factorize(rho, sigma);
+            factor_valid = true; fac_rho = rho; fac_sigma = sigma;
+        }
+        put_panels(xh, x, n);
+        HIPC(hipMemsetAsync(xp, 0, sizeof(T) * (size_t)CP * (size_t)n, st));                        // :38
+        for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); // :39-41
+        std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
+        std::vector<double> resP(count, NAN), resD(count, NAN);
+        for (int b = 0; b < count; ++b) active[b] = 1;
+        auto push_active = [&] {
+            for (int b = 0; b < CP; ++b) h_int[b] = active[b];
+            HIPC(hipMemcpyAsync(d_active, h_int, sizeof(int) * CP, hipMemcpyHostToDevice, st));
+            HIPC(hipStreamSynchronize(st));   // the pinned staging is reused
+        };
+        push_active();
+        const double t1 = now_s();
+        LdlPanelState<T> s; s.x = x; s.xp = xp; s.q = q; s.z = z; s.zp = zp; s.y = y; s.l = l; s.u = u; s.active = d_active; s.npanel = npanel;
+        int nactive = count; bool rhs_ready = false;
+        for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
+            pf.lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one sample of each category in 50 iterations
+            ldl->iterate_panels(s, alpha, rho, sigma, rhs_ready, pf);                               // LinearSystemSolvers.jl:37-40, SolveQuadraticProgram.jl:56-61
+            rhs_ready = true;
+            if (ii % p.numItrConv != 0) continue;                                                   // :63
+            {
+                ProfScope ps(prof, cat_chk, 2);
+                HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long) * (size_t)CP, st));
+                csr_panel<T>(st, A, x, (int)n, Ax, (int)m, npanel);                                 // mA * vX
+                csr_panel<T>(st, P, x, (int)n, Px, (int)n, npanel);                                 // mP * vX
+                csr_panel<T>(st, At, y, (int)m, Aty, (int)n, npanel);                               // mA' * vY
+                shared_check<T>(st, (int)n, (int)m, (int)n, (int)m, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho);   // :64
+            }
+            HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            prof.harvest();
+            bool any_done = false;
+            for (int b = 0; b < count; ++b) {
+                if (!active[b]) continue;
+                const double* r = res_host + 8 * b;
+                resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
+                if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
+            }
+            if (any_done && nactive > 0) push_active();
+        }
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+        const double t2 = now_s();
+        get_panels(x, xh, n);
+        for (int b = 0; b < count && infos; ++b) {
+            qps_info& in = infos[b];
+            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = 0; in.cgIterations = 0;
+            in.rhoFinal = rho; in.rhoProposed = rho; in.resPrim = resP[b]; in.resDual = resD[b];
+            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = 0;   // wall time of the whole batch
+            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
+            in.trsvBlock = 0; in.sweepVariant = 0; in.sweepGaveUp = 0; in.cgExplicit = 0;
+        }
+    }
+};
+
+// =================================================================================================================
 // handle plumbing
 // =================================================================================================================
 struct Handle { SolverBase* impl = nullptr; std::vector<SolverBase*> batch; BatchSolverBase* fused_batch = nullptr; ProxQpBase* proxqp = nullptr; int64_t n = 0, m = 0; std::string err; };
@@ -1329,6 +1494,56 @@ QPS_API int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t 
         auto load = [&](auto s) { s->load(P, ldp, A, lda, q, l, u); h->fused_batch = s.release(); };   // a unique_ptr: a throw while loading drops the solver
         if (dtype == QPS_F64) load(std::make_unique<SharedBatchSolver<double>>(device, (int)count, n, m));
         else load(std::make_unique<SharedBatchSolver<float>>(device, (int)count, n, m));
+    });
+    if (rc != QPS_OK) { delete h; return rc; }
+    *out = reinterpret_cast<qps_handle>(h);
+    return QPS_OK;
+}
+
+QPS_API int32_t qps_create_csc_shared_batch(int64_t count, int64_t n, int64_t m, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const int64_t* Acp,
+                                            const int64_t* Ari, const double* Anz, const double* q, const double* l, const double* u, int32_t index_base,
+                                            int32_t dtype, int32_t device, qps_handle* out) {
+    if (!out) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "out handle pointer is NULL");
+    *out = nullptr;
+    if (count <= 0 || count > 65535) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "batch count must be in 1..65535");
+    if (n <= 0 || m < 0) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "need n >= 1 and m >= 0");
+    if (n + m > ((int64_t)1 << 27) - 64) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "KKT matrix too large for the panel form of the sparse direct plugin (n + m < 2^27)");
+    if (!Pcp || !q || !Acp || (m > 0 && (!l || !u))) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "NULL problem array");
+    if (index_base != 0 && index_base != 1) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "index_base must be 0 or 1");
+    if (dtype != QPS_F64 && dtype != QPS_F32) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "unknown dtype");
+    {   // colptr / rowval / nzval of both matrices, as qps_create_csc
+        std::string why;
+        int vc = layout::validate_csc(n, n, Pcp, Pri, Pnz, index_base, "P", &why);
+        if (vc == 0) vc = layout::validate_csc(m, n, Acp, Ari, Anz, index_base, "A", &why);
+        if (vc != 0) return fail_with(nullptr, vc, why);
+    }
+    if (!all_finite(q, count * n, false)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "q contains NaN/Inf");
+    if (m > 0 && (!all_finite(l, count * m, true) || !all_finite(u, count * m, true))) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "l/u contain NaN");
+    {
+        int64_t bad = -1;
+        int src = guarded(nullptr, [&] { bad = layout::csc_asymmetry(n, Pcp, Pri, Pnz, index_base); });   // SolveQuadraticProgram.m:166-168
+        if (src != QPS_OK) return src;
+        if (bad >= 0) { char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)bad); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b); }
+    }
+    if (m == 0) return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch needs m >= 1 (without constraints the columns are independent linear solves)");
+    if (Pcp[n] - index_base > 2000000000LL || Acp[n] - index_base > 2000000000LL) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "more than 2^31 non-zeros");
+    // ordering + symbolic factor: host only, once per family; the limits are read here, as SparseSolver::ldl_prepare reads them (part of the handle's layout)
+    SparseSharedInput in;
+    int rc = guarded(nullptr, [&] {
+        layout::canonical_csc(n, Pcp, Pri, Pnz, index_base, in.Pcp, in.Pri, in.Pnz);
+        layout::canonical_csc(n, Acp, Ari, Anz, index_base, in.Acp, in.Ari, in.Anz);
+        const char *e1 = getenv("QPS_LDL_MAX_TAIL"), *e2 = getenv("QPS_LDL_MIN_LEVEL"), *e3 = getenv("QPS_LDL_MAX_LEVELS"), *e4 = getenv("QPS_LDL_PANEL_SPR");
+        const int max_tail = e1 ? atoi(e1) : 8192, min_level = e2 ? atoi(e2) : 64, max_levels = e3 ? atoi(e3) : 4096;
+        in.spr = e4 ? atoi(e4) : 0;   // 1 | 4 | 16: that strip count for every level of this handle; anything else: automatic
+        try { in.sym = ldl_analyze((int)n, (int)m, in.Pcp.data(), in.Pri.data(), in.Acp.data(), in.Ari.data(), 0, max_tail, min_level, max_levels); }
+        catch (const std::runtime_error& e) { throw QpsError(QPS_ERR_UNSUPPORTED, e.what()); }
+    });
+    if (rc != QPS_OK) return rc;
+    if (const int dc = require_device(device)) return dc;
+    Handle* h = new Handle(); h->n = n; h->m = m;
+    rc = guarded(nullptr, [&] {
+        if (dtype == QPS_F64) h->fused_batch = new SparseSharedBatchSolver<double>(device, (int)count, n, m, std::move(in), q, l, u);
+        else h->fused_batch = new SparseSharedBatchSolver<float>(device, (int)count, n, m, std::move(in), q, l, u);
     });
     if (rc != QPS_OK) { delete h; return rc; }
     *out = reinterpret_cast<qps_handle>(h);

@@ -138,6 +138,7 @@ enum class SharedPanelOp {
     product,      // out = Mat B                                                     (the check's A x, P x, A'y)
     rhs,          // out = sigma x - q + Mat B                                       LinearSystemSolvers.jl:134-136 with Mat = A', B = rho z - y
     forward,      // out = tril(Mat) B                                               forward sweep over the sweep matrix S (one inverted block)
+    backward,     // out = triu(Mat) B                                               backward sweep alone (dense tail of the sparse shared batch)
     backward_x,   // out = triu(Mat) B; active columns: xp = x, x = alpha out + (1 - alpha) x      backward sweep + SolveQuadraticProgram.jl:56-57
     rows_zy       // s = Mat B = z~; active columns: zp = z, z, y updated, w = rho z - y           SolveQuadraticProgram.jl:59-61
 };
@@ -149,6 +150,12 @@ template <typename T>
 void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* Ax, const T* Px, const T* Aty, const T* q, const T* x, const T* xp,
                   const T* z, const T* zp, unsigned long long* slots, double* res_dev, const int* active, double epsAbs, double epsRel, double epsAdmm,
                   double rho);
+// out[panel][r][16] = sum_k M[r][k] B[panel][k][16] for a plain CSR matrix (k_csr_panel.hip): the check's products of the sparse shared batch.  One 16-lane
+// row per (matrix row, panel), spr strips of it for long rows (csr_panel_spr: from the mean row length), fixed summation order, no atomics.
+// rowsB / rowsOut: rows per panel of B / out.
+template <typename T> struct CsrPanelMatrix { int rows = 0; const int* rp = nullptr; const int* ci = nullptr; const T* va = nullptr; int spr = 1; };
+int csr_panel_spr(int64_t nnz, int rows);
+template <typename T> void csr_panel(hipStream_t st, const CsrPanelMatrix<T>& M, const T* B, int rowsB, T* out, int rowsOut, int npanel);
 template <typename T> void to_panels(hipStream_t st, const double* src, int count, int len, int rowsP, T* dst);     // [count][len] doubles -> panels
 template <typename T> void from_panels(hipStream_t st, const T* src, int count, int len, int rowsP, double* dst);   // panels -> [count][len] doubles
 template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int64_t lds, int rows, int cols, T* dst, int64_t ldd);   // dims multiples of 32

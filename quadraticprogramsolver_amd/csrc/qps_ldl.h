@@ -9,6 +9,14 @@
 
 namespace qps {
 
+// The ADMM state of a shared-matrix batch in 16-column panels (qps_kernels.h): n-vectors [panel][n][16], m-vectors [panel][m][16], one `active` word per column.
+template <typename T> struct LdlPanelState {
+    T *x = nullptr, *xp = nullptr; const T* q = nullptr; T *z = nullptr, *zp = nullptr, *y = nullptr; const T *l = nullptr, *u = nullptr;
+    const int* active = nullptr; int npanel = 0;
+};
+// Profiler categories of iterate_panels (prof == nullptr or a level below lvl: no events)
+struct LdlPanelProf { Profiler* prof = nullptr; int lvl = 2; int cat_rhs = 0, cat_fwd = 0, cat_tail = 0, cat_bwd = 0, cat_post = 0; };
+
 template <typename T> struct SparseLdl {
     virtual ~SparseLdl() {}
     // numeric L D L' of K(rho, sigma) on the device; symbolic data is reused (the changedRho branch :30-32 / :61-63 / :93-95)
@@ -23,6 +31,13 @@ template <typename T> struct SparseLdl {
     // K(rho, sigma) [out_x; out_nu] = [r1; r2] with the factor of the last factorize(): the multiplier block comes back as it is
     // (solve() folds it into z~ = z + (nu - y) / rho, which loses nu when rho is huge)
     virtual void solve_raw(const T* r1, const T* r2, T* out_x, T* out_nu) = 0;
+    // Panel forms (shared-matrix batch: many right-hand sides on one factor).  panels_prepare allocates the permuted right-hand side [panel][N][16] and the tail
+    // vectors [panel][ldt][16]; spr = 1 | 4 | 16 forces that strip count for every level (0: per level from the mean row length).  iterate_panels is iterate() for
+    // every column at once: a column whose active word is 0 keeps its x, xp, z, zp, y.  The summation order of an element depends on the factor's pattern and the
+    // strip count only, so a column does not see the batch around it.
+    virtual void panels_prepare(int npanel, int spr) = 0;
+    virtual void iterate_panels(const LdlPanelState<T>& s, double alpha, double rho, double sigma, bool rhs_ready, const LdlPanelProf& pf) = 0;
+    virtual int panel_launches_per_solve() const = 0;
     virtual const LdlSymbolic& symbolic() const = 0;
     virtual int launches_per_solve() const = 0;
     virtual double bytes_per_solve() const = 0;

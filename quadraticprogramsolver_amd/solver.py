@@ -304,6 +304,8 @@ class QuadraticProgramSharedBatch(_Handle):
                                                             _dp(q), _dp(l), _dp(u), dt, device, C.byref(h)))
         self._h = h
 
+    _linsys = QPS_LINSYS_AUTO          # what solve() passes as qps_params.linsys (the library's default)
+
     def _rows(self, M, name, length):
         a = np.ascontiguousarray(np.atleast_2d(np.asarray(M, dtype=np.float64)))
         if a.shape != (self.count, length):
@@ -331,6 +333,7 @@ class QuadraticProgramSharedBatch(_Handle):
         p.adptRho, p.fctrRho, p.numItrConv = int(bool(adptΡ)), float(fctrΡ), int(numItrConv)
         p.trsvBlock, p.reuseFactor = int(trsvBlock), int(bool(reuseFactor))
         p.polish, p.numItrPolish, p.delta, p.epsMinres, p.numItrMinres = int(bool(polish)), int(numItrPolish), float(δ), float(ϵMinres), int(numItrMinres)
+        p.linsys = self._linsys
         infos = (QpsInfo * self.count)()
         _lib.check(_lib.lib().qps_solve_batch(self._h, _dp(X), C.byref(p), infos), self._h)
         return X, [ConvergenceFlag(i.convFlag) for i in infos], [i.as_dict() for i in infos]
@@ -341,6 +344,40 @@ class QuadraticProgramSharedBatch(_Handle):
         Y = np.zeros((self.count, self.m))
         _lib.check(_lib.lib().qps_get_dual(self._h, _dp(Z), _dp(Y)), self._h)
         return Z, Y
+
+
+class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
+    """``count`` QPs on ONE sparse ``mP`` and ONE sparse ``mA`` (qps_create_csc_shared_batch): the lasso / Huber / SVM regularisation paths and scenario
+    sweeps whose matrices are too large and too sparse for the reduced dense form.  ``mP`` / ``mA`` are scipy sparse or dense and go to the library as
+    CSC; ``mQ`` is [count x n], ``mL`` / ``mU`` are [count x m].  The linear system is the sparse L D L' of the KKT matrix: ordering and symbolic factor
+    once at creation, one numeric factorisation for all columns, every iteration sweeps 16 columns per launch.  Every column behaves as a stand-alone
+    ``QuadraticProgram(..., linsys="ldl")`` solve with a fixed ρ (``adptΡ``, ``polish`` and a ``linsys`` other than "auto" / "ldl" are refused with
+    QPS_ERR_UNSUPPORTED; ``trsvBlock`` is accepted and without effect).  ``update``, ``solve`` and ``dual`` are those of ``QuadraticProgramSharedBatch``."""
+
+    def __init__(self, mP, mA, mQ, mL, mU, *, dtype="f64", device=0):
+        if getattr(mP, "ndim", 0) != 2 or getattr(mA, "ndim", 0) != 2:
+            raise ValueError("mP and mA must be matrices")
+        self.n, self.m = mP.shape[0], mA.shape[0]
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(mQ, dtype=np.float64)))
+        self.count = q.shape[0]
+        l, u = self._rows(mL, "mL", self.m), self._rows(mU, "mU", self.m)
+        _validate_dims(self.n, mP, q[0], mA, l[0], u[0])          # (every row of mQ / mL / mU has the length of the first)
+        Pc = sp.csc_matrix(mP, dtype=np.float64)
+        Ac = sp.csc_matrix(mA, dtype=np.float64)
+        Pc.sum_duplicates()
+        Ac.sum_duplicates()
+        Pcp, Pri, Pnz = Pc.indptr.astype(np.int64), Pc.indices.astype(np.int64), np.ascontiguousarray(Pc.data)
+        Acp, Ari, Anz = Ac.indptr.astype(np.int64), Ac.indices.astype(np.int64), np.ascontiguousarray(Ac.data)
+        h = C.c_void_p()
+        dt = {"f64": QPS_F64, "f32": QPS_F32}[dtype]
+        _lib.check(_lib.lib().qps_create_csc_shared_batch(self.count, self.n, self.m, _ip(Pcp), _ip(Pri), _dp(Pnz), _ip(Acp), _ip(Ari), _dp(Anz),
+                                                          _dp(q), _dp(l), _dp(u), 0, dt, device, C.byref(h)))
+        self._h = h
+
+    def solve(self, mX=None, *, linsys="auto", **kw):
+        """As ``QuadraticProgramSharedBatch.solve``; ``linsys`` ("auto" or "ldl": the sparse L D L' either way) goes to the library as it is."""
+        self._linsys = {"cholesky": QPS_LINSYS_CHOLESKY, "cg": QPS_LINSYS_CG, "cg_explicit": QPS_LINSYS_CG_EXPLICIT, "ldl": QPS_LINSYS_KKT_LDL, "auto": QPS_LINSYS_AUTO}[linsys]
+        return super().solve(mX, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------------------
