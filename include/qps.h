@@ -229,6 +229,21 @@ int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t m, const
                                       const double *q, const double *l, const double *u, int32_t dtype, int32_t device, qps_handle *out);
 int32_t qps_update_shared_vectors(qps_handle h, const double *q, const double *l, const double *u);
 
+/* Per-constraint rho scale of a shared-matrix batch handle (dense or sparse; section 5.2 of the OSQP paper): `scale` is [m], finite and strictly positive, and is
+ * shared by all columns -- which rows are equalities is a property of the family.  Row i then runs with rho_i = rho * scale[i], i.e. the loop of
+ * SolveQuadraticProgram.jl:54-61 with rho read as diag(rho_i): (P + sigma I + A' diag(rho_i) A) x~ = sigma x - q + A'(rho_i z_i - y_i) (dense handle) or the KKT
+ * system with -1 / rho_i on the diagonal of constraint row i (sparse handle), z_i = clamp(alpha z~_i + (1 - alpha) z_i + y_i / rho_i, l_i, u_i),
+ * y_i += rho_i (alpha z~_i + (1 - alpha) z_i - z_i_new).  CheckConvergence is unchanged (none of its norms involves rho); qps_params.rho stays the base value and
+ * rhoFinal / rhoProposed keep reporting it; every column keeps its own check, flag and stopping iteration; adptRho stays refused.  rho_i and 1 / rho_i are formed in
+ * double on the host and rounded once to the handle's type.  One factorisation still serves every column.
+ * The vector is copied (the caller may free it on return).  scale = NULL goes back to the scalar rho and releases what the scale needed on the device (dense handle:
+ * one more m x n matrix, diag(sqrt(scale)) A, from which A' diag(scale) A is formed as a symmetric product, and three vectors of length m; sparse handle: two).
+ * Setting or clearing a scale invalidates the factorisation: the next qps_solve_batch factorises even with reuseFactor = 1; after that reuseFactor and
+ * qps_update_shared_vectors behave as before.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, or an entry that is NaN, Inf, zero or negative (checked before a device is needed; the handle keeps its previous scale and
+ * factor).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch. */
+int32_t qps_set_shared_rho_scale(qps_handle h, const double *scale /* [m]; NULL = back to the scalar rho */);
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads

@@ -396,6 +396,19 @@ function SharedBatchUpdate!(sb::SharedBatchHip; mQ::Union{Nothing, Matrix{Float6
     return nothing
 end
 
+# Per-constraint ρ scale shared by all columns (qps_set_shared_rho_scale): row i runs with ρ_i = ρ vS[i]; vS has m finite, strictly positive entries.
+# nothing goes back to the scalar ρ.  Either way the next SharedBatchSolve! factorises, also with reuseFactor = true.
+function SharedBatchSetRhoScale!(sb::SharedBatchHip, vS::Union{Nothing, Vector{Float64}} = nothing)
+    h = sb.h
+    (vS === nothing || length(vS) == sb.m) || throw(DimensionMismatch("vS must have m elements"))
+    p = vS === nothing ? Ptr{Float64}(C_NULL) : pointer(vS)
+    GC.@preserve vS _check(ccall((:qps_set_shared_rho_scale, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}), h, p), h)
+    return nothing
+end
+
+# factor on the rows that are equalities (l == u) in every column of mL / mU (m x count), 1 elsewhere
+EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
+
 function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIterations = 5000, ϵAbs = 1e-6, ϵRel = 1e-6, ρ = 1, σ = 1e-6, α = 1.6,
     numItrConv = 25, reuseFactor::Bool = false)
     h = sb.h; count = sb.count

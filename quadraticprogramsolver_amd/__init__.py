@@ -5,11 +5,11 @@ from .generator import (GenerateDenseBenchmarkQP, GenerateRandomQP, GenerateSpar
                         SaveQpModel, make_rng, sprandn)
 from .solver import (AutoLinearSolverMode, ConvergenceFlag, HipCg, HipCgInit, HipItrSolCg, HipItrSolCgInit, HipLdl, HipLdlInit, HipChol, HipCholF32, HipCholF32Init, HipCholInit,
                      LinearSolverMode, QuadraticProgram, QuadraticProgramBatch, QuadraticProgramSharedBatch, QuadraticProgramSparseSharedBatch, SolveQuadraticProgram, SolveQuadraticProgram_b,
-                     SolveQuadraticProgramInplace)
+                     SolveQuadraticProgramInplace, equality_rho_scale)
 from .proxqp import ProxQP, SolveQuadraticProgramProxQP
 from ._lib import QpsError, QpsLibraryError
 
 __all__ = ["GenerateRandomQP", "GenerateDenseBenchmarkQP", "GenerateSparseBenchmarkQP", "ProblemClass", "make_rng",
            "sprandn", "SaveQpModel", "LoadQpModel", "ConvergenceFlag", "LinearSolverMode", "QuadraticProgram", "QuadraticProgramBatch", "QuadraticProgramSharedBatch", "QuadraticProgramSparseSharedBatch", "SolveQuadraticProgram",
            "SolveQuadraticProgramInplace", "SolveQuadraticProgram_b", "HipCholInit", "HipChol", "HipCgInit", "HipCg", "HipItrSolCgInit", "HipItrSolCg", "HipLdlInit", "HipLdl", "AutoLinearSolverMode",
-           "HipCholF32Init", "HipCholF32", "ProxQP", "SolveQuadraticProgramProxQP", "QpsError", "QpsLibraryError"]
+           "HipCholF32Init", "HipCholF32", "ProxQP", "SolveQuadraticProgramProxQP", "QpsError", "QpsLibraryError", "equality_rho_scale"]

@@ -47,6 +47,17 @@ __global__ __launch_bounds__(256) void k_ldl_diag0(int N, int Ns, int ldt, const
     const T d = sign[i] > 0 ? ((dposP[i] >= 0 ? kval[dposP[i]] : T(0)) + sigma) : neg_rho1;
     if (i < Ns) D0[i] = d; else Mt[(int64_t)(i - Ns) * ldt + (i - Ns)] = d;
 }
+// the same with rho read as diag(rho_i): constraint row i of the caller (perm[k] - n for the permuted index k) gets -1 / rho_i
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_diag0_rows(int N, int Ns, int ldt, int n, const int* __restrict__ perm, const int* __restrict__ dposP,
+                                                        const signed char* __restrict__ sign, const T* __restrict__ kval, T sigma, const T* __restrict__ rho1_row,
+                                                        T* __restrict__ D0, T* __restrict__ Mt) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= Ns + ldt) return;
+    if (i >= N) { Mt[(int64_t)(i - Ns) * ldt + (i - Ns)] = T(1); return; }
+    const T d = sign[i] > 0 ? ((dposP[i] >= 0 ? kval[dposP[i]] : T(0)) + sigma) : -rho1_row[perm[i] - n];
+    if (i < Ns) D0[i] = d; else Mt[(int64_t)(i - Ns) * ldt + (i - Ns)] = d;
+}
 // D_j = K_jj - sum_k L_jk^2 D_k for the columns [c0, c1) of one level (their rows of L only hold columns of earlier levels)
 template <typename T>
 __global__ __launch_bounds__(256) void k_ldl_level_diag(int c0, int c1, const int* __restrict__ rp, const int* __restrict__ ci, const T* __restrict__ vr,
@@ -255,6 +266,21 @@ __global__ __launch_bounds__(256) void k_ldl_rhs_panel(int N, int n, int m, cons
     }
     b[((int64_t)P * N + k) * 16 + col] = v;
 }
+// k_ldl_rhs_panel with rho read as diag(rho_i): rho1_row is indexed by the caller's row o - n
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_rhs_panel_rows(int N, int n, int m, const int* __restrict__ perm, const T* __restrict__ x, const T* __restrict__ q,
+                                                            const T* __restrict__ z, const T* __restrict__ y, const int* __restrict__ active, T sigma,
+                                                            const T* __restrict__ rho1_row, T* __restrict__ b) {
+    const int e = blockIdx.x * 256 + threadIdx.x, k = e >> 4, col = e & 15, P = blockIdx.y;
+    if (k >= N) return;
+    const int o = perm[k];
+    T v = T(0);
+    if (active[P * 16 + col]) {
+        if (o < n) { const int64_t i = ((int64_t)P * n + o) * 16 + col; v = sigma * x[i] - q[i]; }                      // LinearSystemSolvers.jl:37
+        else { const int64_t i = ((int64_t)P * m + (o - n)) * 16 + col; v = z[i] - rho1_row[o - n] * y[i]; }            // :38
+    }
+    b[((int64_t)P * N + k) * 16 + col] = v;
+}
 // forward substitution for the rows [r0, r1) of one level (or of the tail), one (row, panel) per 16 SPR lanes
 template <typename T, int SPR>
 __global__ __launch_bounds__(PS_THREADS) void k_ldl_fwd_panel(int r0, int r1, int N, int Ns, int ldt, const int* __restrict__ rp, const int* __restrict__ ci,
@@ -310,6 +336,42 @@ __global__ __launch_bounds__(256) void k_ldl_post_update_panel(int n, int m, int
         b[bi] = sigma * xn - q[i];                                            // next :37
     } else {
         const int64_t i = ((int64_t)P * m + (o - n)) * 16 + col;
+        const T zo = z[i], yo = y[i];
+        const T zt = zo + rho1 * (v - yo);                                    // LinearSystemSolvers.jl:40  nu -> z~
+        zp[i] = zo;                                                           // :59
+        const T t = alpha * zt + alpha1 * zo + rho1 * yo;                     // :60
+        const T lo = l[i], hi = u[i];
+        const T zn = t > hi ? hi : (t < lo ? lo : t);
+        z[i] = zn;
+        const T yn = yo + rho * (alpha * zt + alpha1 * zo - zn);              // :61
+        y[i] = yn;
+        b[bi] = zn - rho1 * yn;                                               // next :38
+    }
+}
+// k_ldl_post_update_panel with rho read as diag(rho_i): row o - n of the caller takes rho_row[o - n] and rho1_row[o - n]
+template <typename T>
+__global__ __launch_bounds__(256) void k_ldl_post_update_panel_rows(int n, int m, int N, int Ns, int ldt, const int* __restrict__ iperm, T* __restrict__ b,
+                                                                    const T* __restrict__ tx, const T* __restrict__ q, T* __restrict__ x, T* __restrict__ xp,
+                                                                    T* __restrict__ z, T* __restrict__ zp, T* __restrict__ y, const T* __restrict__ l,
+                                                                    const T* __restrict__ u, const int* __restrict__ active, T alpha, T sigma,
+                                                                    const T* __restrict__ rho_row, const T* __restrict__ rho1_row) {
+    const int e = blockIdx.x * 256 + threadIdx.x, o = e >> 4, col = e & 15, P = blockIdx.y;
+    if (o >= n + m) return;
+    const int k = iperm[o];
+    const int64_t bi = ((int64_t)P * N + k) * 16 + col;
+    if (!active[P * 16 + col]) { b[bi] = T(0); return; }
+    const T v = k >= Ns ? tx[((int64_t)P * ldt + (k - Ns)) * 16 + col] : b[bi];       // every thread reads its own b entry before it overwrites it
+    const T alpha1 = T(1) - alpha;
+    if (o < n) {
+        const int64_t i = ((int64_t)P * n + o) * 16 + col;
+        const T xo = x[i];
+        xp[i] = xo;                                                           // :56
+        const T xn = alpha * v + alpha1 * xo;                                 // :57
+        x[i] = xn;
+        b[bi] = sigma * xn - q[i];                                            // next :37
+    } else {
+        const int64_t i = ((int64_t)P * m + (o - n)) * 16 + col;
+        const T rho = rho_row[o - n], rho1 = rho1_row[o - n];
         const T zo = z[i], yo = y[i];
         const T zt = zo + rho1 * (v - yo);                                    // LinearSystemSolvers.jl:40  nu -> z~
         zp[i] = zo;                                                           // :59
@@ -405,6 +467,7 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
     std::vector<int> group_ptr; int KC = 16, GS = 1, nb = 64; bool tail_signed = false;   // Schur complement: groups of GS K-slices of KC columns
     DevVec<T> slabs;
     std::vector<int> lpr_fwd, lpr_bwd; int lpr_tail = 1;
+    const T *row_rho = nullptr, *row_rho1 = nullptr;   // set_row_rho: rho_i, 1 / rho_i by the caller's row (not owned)
     DevVec<T> bP, tbP, tuP, txP; int npanel = 0; std::vector<int> spr_fwd, spr_bwd; int spr_tail = 1;   // panel forms (panels_prepare)
 
     SparseLdlImpl(hipStream_t st_, LdlSymbolic&& sym, const double* Pv, int64_t pnnz, const double* Av, int64_t annz) : st(st_), S(std::move(sym)) {
@@ -486,7 +549,8 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
         if (ldt > 0) HIPC(hipMemsetAsync(Mt.p, 0, sizeof(T) * (size_t)ldt * ldt, st));
         const int64_t ne = (int64_t)S.k_dst.size();
         if (ne > 0) hipLaunchKernelGGL((k_ldl_scatter<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, ne, kdst.p, ksrc.p, kval.p, vr.p, Mt.p);
-        hipLaunchKernelGGL((k_ldl_diag0<T>), dim3((Ns + ldt + 255) / 256), dim3(256), 0, st, N, Ns, ldt, dposP.p, sign.p, kval.p, (T)sigma, (T)(-1.0 / rho), D0.p, Mt.p);
+        if (row_rho1) hipLaunchKernelGGL((k_ldl_diag0_rows<T>), dim3((Ns + ldt + 255) / 256), dim3(256), 0, st, N, Ns, ldt, S.n, perm.p, dposP.p, sign.p, kval.p, (T)sigma, row_rho1, D0.p, Mt.p);
+        else hipLaunchKernelGGL((k_ldl_diag0<T>), dim3((Ns + ldt + 255) / 256), dim3(256), 0, st, N, Ns, ldt, dposP.p, sign.p, kval.p, (T)sigma, (T)(-1.0 / rho), D0.p, Mt.p);
         const int L = (int)S.level_ptr.size() - 1;
         for (int l = 0; l < L; ++l) {
             const int c0 = S.level_ptr[l], c1 = S.level_ptr[l + 1];
@@ -565,6 +629,7 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
         spr_tail = forced ? spr : pick_panel_spr((int64_t)S.rp[N] - S.rp[Ns], Nt);
     }
     int panel_launches_per_solve() const override { return launches_per_solve(); }
+    void set_row_rho(const T* rho_row, const T* rho1_row) override { row_rho = rho_row; row_rho1 = rho1_row; }
     template <int SPR> void fwd_panel_launch(int r0, int r1) {
         constexpr int RPB = PS_THREADS / (16 * SPR);
         hipLaunchKernelGGL((k_ldl_fwd_panel<T, SPR>), dim3((unsigned)((r1 - r0 + RPB - 1) / RPB), (unsigned)npanel), dim3(PS_THREADS), 0, st, r0, r1, S.N, S.Ns, S.ldt,
@@ -584,7 +649,8 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
         const dim3 gN((unsigned)(((int64_t)N * 16 + 255) / 256), (unsigned)npanel);
         if (!rhs_ready) {
             ProfScope ps(pr, pf.cat_rhs, pf.lvl);
-            hipLaunchKernelGGL((k_ldl_rhs_panel<T>), gN, dim3(256), 0, st, N, S.n, S.m, perm.p, s.x, s.q, s.z, s.y, s.active, (T)sigma, (T)(1.0 / rho), bP.p);
+            if (row_rho) hipLaunchKernelGGL((k_ldl_rhs_panel_rows<T>), gN, dim3(256), 0, st, N, S.n, S.m, perm.p, s.x, s.q, s.z, s.y, s.active, (T)sigma, row_rho1, bP.p);
+            else hipLaunchKernelGGL((k_ldl_rhs_panel<T>), gN, dim3(256), 0, st, N, S.n, S.m, perm.p, s.x, s.q, s.z, s.y, s.active, (T)sigma, (T)(1.0 / rho), bP.p);
         }
         {
             ProfScope ps(pr, pf.cat_fwd, pf.lvl);
@@ -606,7 +672,9 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
         }
         {
             ProfScope ps(pr, pf.cat_post, pf.lvl);
-            hipLaunchKernelGGL((k_ldl_post_update_panel<T>), gN, dim3(256), 0, st, S.n, S.m, N, Ns, ldt, iperm.p, bP.p, txP.p, s.q, s.x, s.xp, s.z, s.zp, s.y, s.l, s.u,
+            if (row_rho) hipLaunchKernelGGL((k_ldl_post_update_panel_rows<T>), gN, dim3(256), 0, st, S.n, S.m, N, Ns, ldt, iperm.p, bP.p, txP.p, s.q, s.x, s.xp, s.z, s.zp,
+                                            s.y, s.l, s.u, s.active, (T)alpha, (T)sigma, row_rho, row_rho1);
+            else hipLaunchKernelGGL((k_ldl_post_update_panel<T>), gN, dim3(256), 0, st, S.n, S.m, N, Ns, ldt, iperm.p, bP.p, txP.p, s.q, s.x, s.xp, s.z, s.zp, s.y, s.l, s.u,
                                s.active, (T)alpha, (T)rho, (T)sigma);
         }
     }

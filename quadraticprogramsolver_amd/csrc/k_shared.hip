@@ -124,7 +124,8 @@ struct PanelStep {
 };
 
 // EPI: 0 out = s;  1 out = sigma x - q + s (right-hand side, LinearSystemSolvers.jl:136);  2 s = x~: out = s, xp = x, x = alpha s + (1 - alpha) x
-// (SolveQuadraticProgram.jl:56-57);  3 s = z~: zp = z, z = clamp(...), y += rho (...), w = rho z - y (:59-61 and the next :134-135)
+// (SolveQuadraticProgram.jl:56-57);  3 s = z~: zp = z, z = clamp(...), y += rho (...), w = rho z - y (:59-61 and the next :134-135);
+// 4 = 3 with rho read as diag(rho_i): rho_i and 1 / rho_i of the output row come from a.rho_row / a.rho1_row (two cached loads per output element)
 template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
 __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
     using S = PanelStep<T, TRI, PB, STG>;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
                 a.xp[idx] = xo;                                          // :56
                 a.x[idx] = a.alpha * sum + alpha1 * xo;                  // :57
             }
-        } else {
+        } else if (EPI == 3) {
             if (a.active[P * 16 + col]) {
                 const T zo = a.z[idx], yo = a.y[idx];
                 a.zp[idx] = zo;                                          // :59
@@ -206,6 +207,18 @@ __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
                 const T yn = yo + a.rho * (a.alpha * sum + alpha1 * zo - zn);   // :61
                 a.z[idx] = zn; a.y[idx] = yn;
                 a.w[idx] = a.rho * zn - yn;                              // LinearSystemSolvers.jl:134-135 of the next iteration
+            }
+        } else {
+            if (a.active[P * 16 + col]) {
+                const T rr = a.rho_row[r0 + row], rr1 = a.rho1_row[r0 + row];   // rho_i, 1 / rho_i: r0 + row < a.rows, the vectors' length
+                const T zo = a.z[idx], yo = a.y[idx];
+                a.zp[idx] = zo;                                          // :59
+                const T t = a.alpha * sum + alpha1 * zo + rr1 * yo;      // :60
+                const T lo = a.l[idx], hi = a.u[idx];
+                const T zn = t > hi ? hi : (t < lo ? lo : t);
+                const T yn = yo + rr * (a.alpha * sum + alpha1 * zo - zn);      // :61
+                a.z[idx] = zn; a.y[idx] = yn;
+                a.w[idx] = rr * zn - yn;                                 // LinearSystemSolvers.jl:134-135 of the next iteration
             }
         }
     }
@@ -298,6 +311,15 @@ __global__ __launch_bounds__(256) void k_transpose(const T* __restrict__ src, in
     for (int k = 0; k < 4; ++k) dst[(int64_t)(c0 + ty + 8 * k) * ldd + r0 + tx] = tile[tx][ty + 8 * k];
 }
 
+// dst = diag(scale) src, 16 bytes per lane
+template <typename T>
+__global__ __launch_bounds__(256) void k_scale_rows(const T* __restrict__ src, const T* __restrict__ scale, int64_t vecs, int vpr, T* __restrict__ dst) {
+    typedef T NV __attribute__((ext_vector_type(VecOf<T>::N)));
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= vecs) return;
+    reinterpret_cast<NV*>(dst)[i] = reinterpret_cast<const NV*>(src)[i] * scale[i / vpr];
+}
+
 template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
 void panel_launch(hipStream_t st, const PanelArgs<T>& a) {
     const dim3 grid((a.rows / 16) * ((a.npanel + PB - 1) / PB)), block(SH_NW * 64);
@@ -331,6 +353,7 @@ void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a) {
         case SharedPanelOp::backward: panel_shape<T, 2, 0>(st, a); break;
         case SharedPanelOp::backward_x: panel_shape<T, 2, 2>(st, a); break;
         case SharedPanelOp::rows_zy: panel_shape<T, 0, 3>(st, a); break;
+        case SharedPanelOp::rows_zy_scaled: panel_shape<T, 0, 4>(st, a); break;
     }
 }
 
@@ -357,7 +380,15 @@ template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int6
     hipLaunchKernelGGL((k_transpose<T>), dim3(cols / 32, rows / 32), dim3(256), 0, st, src, lds, dst, ldd);
 }
 
+template <typename T> void scale_rows(hipStream_t st, const T* src, const T* scale, int rows, int cols, T* dst) {
+    const int vpr = cols / VecOf<T>::N;
+    const int64_t vecs = (int64_t)rows * vpr;
+    if (vecs <= 0) return;
+    hipLaunchKernelGGL((k_scale_rows<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, src, scale, vecs, vpr, dst);
+}
+
 #define INST(T)                                                                                                                         \
+    template void scale_rows<T>(hipStream_t, const T*, const T*, int, int, T*);                                                         \
     template void shared_panel<T>(hipStream_t, SharedPanelOp, const PanelArgs<T>&);                                                     \
     template void shared_check<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,     \
                                   const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double);        \

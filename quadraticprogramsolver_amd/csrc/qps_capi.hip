@@ -550,6 +550,8 @@ struct BatchSolverBase {
     virtual void solve_batch(double* x, const qps_params& p, qps_info* infos) = 0;
     virtual void get_dual(double* z, double* y) = 0;   // [count][m] each
     virtual bool update_vectors(const double* q, const double* l, const double* u) { (void)q; (void)l; (void)u; return false; }   // shared-matrix batches only
+    virtual bool takes_rho_scale() const { return false; }                            // shared-matrix batches only
+    virtual void set_rho_scale(const double* scale) { (void)scale; }                  // scale: [m] validated by the caller, or NULL
 };
 
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
@@ -824,6 +826,10 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
     bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
     int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
+    // Per-row rho scale (qps_set_shared_rho_scale): row i runs with rho_i = rho s_i.  Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so
+    // M = PI + rho Ws'Ws comes out of the same symmetric product and a change of the base rho alone only re-assembles; rs_rho / rs_rho1 hold rho_i and 1 / rho_i
+    // (MP long, padding rows: scale 1), formed in double and rounded once, for the base rho rs_base (0: stale).  All four buffers exist only while a scale is set.
+    std::vector<double> rho_scale; T *Ws = nullptr, *rs_sqrt = nullptr, *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
 
     SharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_) {
         device = dev; n = n_; m = m_; count = cnt;
@@ -885,10 +891,41 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         if (zh) get_panels(z, zh, m, MP);
         if (yh) get_panels(y, yh, m, MP);
     }
+    bool takes_rho_scale() const override { return true; }
+    void set_rho_scale(const double* s) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        if (!s) {
+            for (T** v : {&Ws, &rs_sqrt, &rs_rho, &rs_rho1}) { mem.release(*v); *v = nullptr; }
+            rho_scale.clear();
+        } else {
+            if (!Ws) Ws = mem.dalloc<T>((int64_t)MP * NP, st);
+            if (!rs_sqrt) rs_sqrt = mem.dalloc<T>(MP, st);
+            if (!rs_rho) rs_rho = mem.dalloc<T>(MP, st);
+            if (!rs_rho1) rs_rho1 = mem.dalloc<T>(MP, st);
+            std::vector<T> h((size_t)MP, T(1));
+            for (int64_t i = 0; i < m; ++i) h[i] = (T)std::sqrt(s[i]);
+            if (!up) up.reset(new StagedUploader(st));
+            up->copy(rs_sqrt, h.data(), sizeof(T) * (size_t)MP);
+            scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);
+            HIPC(hipStreamSynchronize(st));
+            rho_scale.assign(s, s + m);
+        }
+        factor_valid = false; have_AA = false; rs_base = 0;   // the cached product and the factor belong to the previous scale
+    }
+    void push_row_rho(double rho) {   // rho_i and 1 / rho_i for this base rho
+        if (rs_base == rho) return;
+        std::vector<T> h((size_t)MP), h1((size_t)MP);
+        for (int i = 0; i < MP; ++i) { const double r = rho * (i < m ? rho_scale[i] : 1.0); h[i] = (T)r; h1[i] = (T)(1.0 / r); }
+        up->copy(rs_rho, h.data(), sizeof(T) * (size_t)MP);
+        up->copy(rs_rho1, h1.data(), sizeof(T) * (size_t)MP);
+        HIPC(hipStreamSynchronize(st));
+        rs_base = rho;
+    }
     // LinSysSolInit once for all columns: LinearSystemSolvers.jl:110-122 + factorisation, sweep matrix with one inverted block
     void factorize(double rho, double sigma, bool rebuild_all) {
         const bool rebuild = rebuild_all || !have_AA;
-        const DenseChol<T> c{st, (int)n, NP, MP, P, A, PI, AA, M, S, tmp, dinv, fail};
+        const DenseChol<T> c{st, (int)n, NP, MP, P, rho_scale.empty() ? A : Ws, PI, AA, M, S, tmp, dinv, fail};   // A'A, or A' diag(s) A = Ws'Ws
         factor_valid = false;
         HIPC(hipMemsetAsync(fail, 0, sizeof(int) * 4, st));
         c.form(sigma, rho, rebuild, rebuild);
@@ -914,6 +951,8 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
+        const bool scaled = !rho_scale.empty();
+        if (scaled) push_row_rho(rho);
         if (!reuse) factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma);        // :36
         put_panels(xh, x, n, NP);
         for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
@@ -933,6 +972,8 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         PanelArgs<T> a_bwd = product_args(S, NP, NP, NP, yv, xx); a_bwd.x = x; a_bwd.xp = xp; a_bwd.alpha = (T)alpha;
         PanelArgs<T> a_row = product_args(A, NP, MP, NP, xx, nullptr);
         a_row.z = z; a_row.zp = zp; a_row.y = y; a_row.w = w; a_row.l = l; a_row.u = u; a_row.alpha = (T)alpha; a_row.rho = (T)rho;
+        a_row.rho_row = rs_rho; a_row.rho1_row = rs_rho1;
+        const SharedPanelOp op_row = scaled ? SharedPanelOp::rows_zy_scaled : SharedPanelOp::rows_zy;
         const PanelArgs<T> a_ax = product_args(A, NP, MP, NP, x, Ax), a_px = product_args(P, NP, NP, NP, x, Px), a_aty = product_args(At, MP, NP, MP, y, Aty);
         int nactive = count;
         for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
@@ -940,7 +981,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
             { ProfLaunchScope ps(prof, cat_atw, lvl); shared_panel<T>(st, SharedPanelOp::rhs, a_rhs); }          // LinearSystemSolvers.jl:134-136
             { ProfLaunchScope ps(prof, cat_fwd, lvl); shared_panel<T>(st, SharedPanelOp::forward, a_fwd); }      // :137, L y = t
             { ProfLaunchScope ps(prof, cat_bwd, lvl); shared_panel<T>(st, SharedPanelOp::backward_x, a_bwd); }   // :137, L' x~ = y; SolveQuadraticProgram.jl:56-57
-            { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, SharedPanelOp::rows_zy, a_row); }     // :139; SolveQuadraticProgram.jl:59-61
+            { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, op_row, a_row); }     // :139; SolveQuadraticProgram.jl:59-61
             if (ii % p.numItrConv != 0) continue;                                                   // :63
             {
                 ProfScope ps(prof, cat_chk, 2);
@@ -998,6 +1039,9 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     bool factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
     LdlPanelProf pf; int cat_chk = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
+    // Per-row rho scale (qps_set_shared_rho_scale): rho_i = rho s_i and 1 / rho_i by the caller's row (m long), formed in double and rounded once, for the base
+    // rho rs_base (0: stale); the factor object reads them in its numeric factorisation and panel kernels.  They exist only while a scale is set.
+    std::vector<double> rho_scale; T *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
 
     SparseSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, SparseSharedInput&& in, const double* qh, const double* lh, const double* uh) {
         device = dev; n = n_; m = m_; count = cnt;
@@ -1071,6 +1115,31 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         if (zh) get_panels(z, zh, m);
         if (yh) get_panels(y, yh, m);
     }
+    bool takes_rho_scale() const override { return true; }
+    void set_rho_scale(const double* s) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        if (!s) {
+            ldl->set_row_rho(nullptr, nullptr);
+            for (T** v : {&rs_rho, &rs_rho1}) { mem.release(*v); *v = nullptr; }
+            rho_scale.clear();
+        } else {
+            if (!rs_rho) rs_rho = mem.dalloc<T>(m, st);
+            if (!rs_rho1) rs_rho1 = mem.dalloc<T>(m, st);
+            rho_scale.assign(s, s + m);
+            ldl->set_row_rho(rs_rho, rs_rho1);
+        }
+        factor_valid = false; rs_base = 0;   // the factor belongs to the previous scale
+    }
+    void push_row_rho(double rho) {   // rho_i and 1 / rho_i for this base rho
+        if (rs_base == rho) return;
+        std::vector<T> h((size_t)m), h1((size_t)m);
+        for (int64_t i = 0; i < m; ++i) { const double r = rho * rho_scale[i]; h[i] = (T)r; h1[i] = (T)(1.0 / r); }
+        up->copy(rs_rho, h.data(), sizeof(T) * (size_t)m);
+        up->copy(rs_rho1, h1.data(), sizeof(T) * (size_t)m);
+        HIPC(hipStreamSynchronize(st));
+        rs_base = rho;
+    }
     void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
         HIPC(hipSetDevice(device));
         if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: adptRho is not supported (one factor serves every column, so rho is common and fixed)");
@@ -1080,6 +1149,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
+        if (!rho_scale.empty()) push_row_rho(rho);
         if (!reuse) {                                                                               // :36: numeric factorisation, once for all columns
             factor_valid = false;
             ++num_factorizations;
@@ -1560,6 +1630,19 @@ QPS_API int32_t qps_update_shared_vectors(qps_handle hh, const double* q, const 
     const int rc = guarded(h, [&] { shared = h->fused_batch->update_vectors(q, l, u); });
     if (rc != QPS_OK) return rc;
     return shared ? QPS_OK : fail_with(h, QPS_ERR_BAD_ARGUMENT, "not a shared-matrix batch handle");
+}
+
+QPS_API int32_t qps_set_shared_rho_scale(qps_handle hh, const double* scale) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    const char* other = "qps_set_shared_rho_scale: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) take a per-row rho scale";
+    if (!h->fused_batch || !h->fused_batch->takes_rho_scale()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    for (int64_t i = 0; scale && i < h->m; ++i)
+        if (!(scale[i] > 0) || !std::isfinite(scale[i])) {
+            char b[128]; snprintf(b, sizeof b, "rho scale: entry %lld is not a finite positive number", (long long)i);
+            return fail_with(h, QPS_ERR_BAD_ARGUMENT, b);
+        }
+    return guarded(h, [&] { h->fused_batch->set_rho_scale(scale); });
 }
 
 QPS_API int32_t qps_solve_batch_multi(int64_t count, int64_t n, int64_t m, const double* P, const double* A, const double* q, const double* l, const double* u,

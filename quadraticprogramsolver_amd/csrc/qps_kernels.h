@@ -133,6 +133,7 @@ template <typename T> struct PanelArgs {
     T *z = nullptr, *zp = nullptr, *y = nullptr, *w = nullptr; const T *l = nullptr, *u = nullptr;   // rows_zy
     const int* active = nullptr;                                                                     // one word per column (npanel * 16)
     T alpha = T(0), rho = T(1), sigma = T(0);
+    const T *rho_row = nullptr, *rho1_row = nullptr;                                                 // rows_zy_scaled: rho_i and 1 / rho_i per matrix row (`rows` long)
 };
 enum class SharedPanelOp {
     product,      // out = Mat B                                                     (the check's A x, P x, A'y)
@@ -140,7 +141,8 @@ enum class SharedPanelOp {
     forward,      // out = tril(Mat) B                                               forward sweep over the sweep matrix S (one inverted block)
     backward,     // out = triu(Mat) B                                               backward sweep alone (dense tail of the sparse shared batch)
     backward_x,   // out = triu(Mat) B; active columns: xp = x, x = alpha out + (1 - alpha) x      backward sweep + SolveQuadraticProgram.jl:56-57
-    rows_zy       // s = Mat B = z~; active columns: zp = z, z, y updated, w = rho z - y           SolveQuadraticProgram.jl:59-61
+    rows_zy,      // s = Mat B = z~; active columns: zp = z, z, y updated, w = rho z - y           SolveQuadraticProgram.jl:59-61
+    rows_zy_scaled   // rows_zy with rho read as diag(rho_i): row r takes rho_row[r] and rho1_row[r] in z, y and w (qps_set_shared_rho_scale)
 };
 template <typename T> void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a);
 bool shared_panel_small(int rows, int K, size_t elem);   // matrix small enough to stay cached: one panel and 16 waves per workgroup
@@ -159,6 +161,8 @@ template <typename T> void csr_panel(hipStream_t st, const CsrPanelMatrix<T>& M,
 template <typename T> void to_panels(hipStream_t st, const double* src, int count, int len, int rowsP, T* dst);     // [count][len] doubles -> panels
 template <typename T> void from_panels(hipStream_t st, const T* src, int count, int len, int rowsP, double* dst);   // panels -> [count][len] doubles
 template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int64_t lds, int rows, int cols, T* dst, int64_t ldd);   // dims multiples of 32
+// dst[r][c] = scale[r] * src[r][c] for a row-major rows x cols matrix (ld = cols, a multiple of VecOf<T>::N): W = diag(sqrt(s_i)) A of the per-row rho scale
+template <typename T> void scale_rows(hipStream_t st, const T* src, const T* scale, int rows, int cols, T* dst);
 
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);

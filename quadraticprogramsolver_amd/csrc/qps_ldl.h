@@ -38,6 +38,11 @@ template <typename T> struct SparseLdl {
     virtual void panels_prepare(int npanel, int spr) = 0;
     virtual void iterate_panels(const LdlPanelState<T>& s, double alpha, double rho, double sigma, bool rhs_ready, const LdlPanelProf& pf) = 0;
     virtual int panel_launches_per_solve() const = 0;
+    // rho read as diag(rho_i) (qps_set_shared_rho_scale): device vectors of length m holding rho_i and 1 / rho_i, indexed by the CALLER's row number (the
+    // kernels go through perm / iperm); nullptr, nullptr: back to the scalar.  The next factorize() puts -1 / rho_i on the diagonal of constraint row i -- in
+    // the sparse levels and in the dense tail alike -- and iterate_panels() reads them in its right-hand side and row updates; both then ignore the scalar rho.
+    // solve(), iterate() and solve_raw() of stand-alone handles do not look at them.
+    virtual void set_row_rho(const T* rho_row, const T* rho1_row) = 0;
     virtual const LdlSymbolic& symbolic() const = 0;
     virtual int launches_per_solve() const = 0;
     virtual double bytes_per_solve() const = 0;

@@ -280,6 +280,15 @@ class QuadraticProgramBatch(_Handle):
         return Z[:, :self.m], Y[:, :self.m]
 
 
+def equality_rho_scale(mL, mU, factor=1e3):
+    """The ρ scale of OSQP §5.2 for a family: ``factor`` on the rows that are equalities (l == u) in EVERY column of ``mL`` / ``mU`` ([count x m], or one
+    vector of length m), 1 elsewhere.  What ``QuadraticProgramSharedBatch.set_rho_scale`` takes."""
+    L, U = np.atleast_2d(np.asarray(mL, dtype=np.float64)), np.atleast_2d(np.asarray(mU, dtype=np.float64))
+    if L.shape != U.shape:
+        raise ValueError(f"dimension mismatch: mL has shape {L.shape}, mU has shape {U.shape}")
+    return np.where(np.all(L == U, axis=0), float(factor), 1.0)
+
+
 class QuadraticProgramSharedBatch(_Handle):
     """``count`` QPs on ONE ``mP`` and ONE ``mA`` that differ in ``q``, ``l`` and ``u`` only (qps_create_dense_shared_batch): an MPC horizon
     re-solved every sample, a regularisation path, a scenario sweep.  ``mQ`` is [count x n], ``mL`` / ``mU`` are [count x m].  The matrices are
@@ -320,6 +329,13 @@ class QuadraticProgramSharedBatch(_Handle):
         u = None if mU is None else self._rows(mU, "mU", self.m)
         ptr = lambda a: None if a is None else _dp(a)
         _lib.check(_lib.lib().qps_update_shared_vectors(self._h, ptr(q), ptr(l), ptr(u)), self._h)
+
+    def set_rho_scale(self, vS=None):
+        """Per-constraint ρ scale shared by all columns (qps_set_shared_rho_scale): row i runs with ρ_i = ρ vS[i]; ``vS`` has m finite, strictly
+        positive entries (``equality_rho_scale`` builds the usual one).  ``None`` goes back to the scalar ρ.  Either way the next ``solve``
+        factorises, also with ``reuseFactor=True``; ``ρ`` of ``solve`` stays the base value."""
+        s = None if vS is None else _vec(vS, "vS", self.m)
+        _lib.check(_lib.lib().qps_set_shared_rho_scale(self._h, None if s is None else _dp(s)), self._h)
 
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
