@@ -244,6 +244,24 @@ int32_t qps_update_shared_vectors(qps_handle h, const double *q, const double *l
  * factor).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch. */
 int32_t qps_set_shared_rho_scale(qps_handle h, const double *scale /* [m]; NULL = back to the scalar rho */);
 
+/* Family-wide adaptive rho of a shared-matrix batch handle (dense or sparse).  mode 0 (the default): the fixed rho of qps_params.rho.  mode 1: ONE rho that moves
+ * for the whole family by the reference's own rule (SolveQuadraticProgram.jl:92-96 and :47) with the four norms taken from the worst columns.  At a check, after
+ * the per-column decisions (unchanged), over the columns still running: bp = argmax normResPrim_b / maxNormPrim_b, bd = argmax normResDual_b / maxNormDual_b
+ * (lowest column on ties; a NaN quotient never wins against a number), and
+ *   rhoProposed = clamp(rho * sqrt((normResPrim_bp * maxNormDual_bd) / (normResDual_bd * maxNormPrim_bp)), 1e-3, 1e6);
+ * no running column leaves it alone.  At the top of the next iteration, rhoProposed * fctrRho < rho || rhoProposed > fctrRho * rho makes rho = rhoProposed: one
+ * numeric re-factorisation for the whole batch (dense: assembly from the cached A'A plus Cholesky; sparse: numeric L D L' on the frozen pattern), and every
+ * running column continues on the new factor.  With count = 1 this is the adptRho = 1 loop of a stand-alone handle, expression for expression.  The decision is
+ * taken on the host from the norms it reads at every check anyway.  qps_params.fctrRho of the solve is used (QPS_ERR_BAD_ARGUMENT unless > 0); qps_params.adptRho
+ * names the per-problem rule and stays refused.  With a rho scale set the base rho moves and row i runs with rho * scale[i].
+ * qps_info per column: numRefactor = switches while the column was running, rhoFinal = the rho of its last iteration, rhoProposed = the family proposal after the
+ * check at which it stopped (or at exit), tRefactor = seconds spent in switches (whole batch, like tLoop).
+ * The mode is a property of the handle and persists across solves.  After a solve the factor belongs to the last rho: reuseFactor = 1 with qps_params.rho =
+ * rhoFinal of the column that ran longest factorises nothing -- the re-solve pattern after qps_update_shared_vectors.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle or any other mode (before a device is needed).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is
+ * not a shared-matrix batch. */
+int32_t qps_set_shared_adaptive_rho(qps_handle h, int32_t mode /* 0 fixed rho, 1 family-wide rule */);
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads

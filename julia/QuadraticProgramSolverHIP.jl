@@ -406,14 +406,22 @@ function SharedBatchSetRhoScale!(sb::SharedBatchHip, vS::Union{Nothing, Vector{F
     return nothing
 end
 
+# Family-wide adaptive ρ (qps_set_shared_adaptive_rho): one ρ that moves for all columns by the reference's rule with the norms of the worst running columns;
+# a switch re-factorises once for the whole batch and uses fctrΡ of SharedBatchSolve!.  false goes back to the fixed ρ.  The setting stays with the handle.
+function SharedBatchSetAdaptiveRho!(sb::SharedBatchHip, on::Bool = true)
+    h = sb.h
+    _check(ccall((:qps_set_shared_adaptive_rho, LIBQPS), Int32, (Ptr{Cvoid}, Int32), h, on ? 1 : 0), h)
+    return nothing
+end
+
 # factor on the rows that are equalities (l == u) in every column of mL / mU (m x count), 1 elsewhere
 EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
 
 function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIterations = 5000, ϵAbs = 1e-6, ϵRel = 1e-6, ρ = 1, σ = 1e-6, α = 1.6,
-    numItrConv = 25, reuseFactor::Bool = false)
+    fctrΡ = 5, numItrConv = 25, reuseFactor::Bool = false)
     h = sb.h; count = sb.count
     size(mX) == (sb.n, count) || throw(DimensionMismatch("mX must be n x count: the library reads and writes count columns of length n"))
-    prm = QpsParams(numIterations, 0, numItrConv, 10, 500, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, 1e-6, 5, 1e-6, 1e-6, 1000, 0, 0, 0)
+    prm = QpsParams(numIterations, 0, numItrConv, 10, 500, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, 1e-6, fctrΡ, 1e-6, 1e-6, 1000, 0, 0, 0)
     buf = Vector{UInt8}(undef, count * sizeof(QpsInfo))
     GC.@preserve mX buf _check(ccall((:qps_solve_batch, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
                                      h, mX, Ref(prm), buf), h)

@@ -320,6 +320,29 @@ __global__ __launch_bounds__(256) void k_scale_rows(const T* __restrict__ src, c
     reinterpret_cast<NV*>(dst)[i] = reinterpret_cast<const NV*>(src)[i] * scale[i / vpr];
 }
 
+// w = rho z - y over [panel][MP][16] after a switch of the family rho (qps_set_shared_adaptive_rho): the expression of the EPI == 3 / EPI == 4 epilogues with
+// the new rho, so that the next right-hand side reads what the row update would have left behind.  16 bytes per lane (VN neighbouring columns of one row);
+// a stopped column keeps its w.  SCALED: rho_i of the row from rho_row.
+template <typename T, bool SCALED>
+__global__ __launch_bounds__(256) void k_panel_w(const T* __restrict__ z, const T* __restrict__ y, const int* __restrict__ active, const T* __restrict__ rho_row,
+                                                 T rho, int MP, int64_t vecs, T* __restrict__ w) {
+    constexpr int VN = VecOf<T>::N;
+    typedef T NV __attribute__((ext_vector_type(VN)));
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= vecs) return;
+    const int64_t e = i * VN;                                   // first element: (panel, row, column) = (e / (16 MP), e / 16 % MP, e % 16)
+    const int P = (int)(e / ((int64_t)MP * 16)), row = (int)((e >> 4) % MP), col = (int)(e & 15);
+    const T rr = SCALED ? rho_row[row] : rho;
+    const NV zv = reinterpret_cast<const NV*>(z)[i], yv = reinterpret_cast<const NV*>(y)[i];
+    NV wv = reinterpret_cast<const NV*>(w)[i];
+#pragma unroll
+    for (int j = 0; j < VN; ++j) {
+        const T zn = zv[j], yn = yv[j];
+        if (active[P * 16 + col + j]) wv[j] = rr * zn - yn;
+    }
+    reinterpret_cast<NV*>(w)[i] = wv;
+}
+
 template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
 void panel_launch(hipStream_t st, const PanelArgs<T>& a) {
     const dim3 grid((a.rows / 16) * ((a.npanel + PB - 1) / PB)), block(SH_NW * 64);
@@ -380,6 +403,14 @@ template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int6
     hipLaunchKernelGGL((k_transpose<T>), dim3(cols / 32, rows / 32), dim3(256), 0, st, src, lds, dst, ldd);
 }
 
+template <typename T> void panel_w(hipStream_t st, const T* z, const T* y, const int* active, const T* rho_row, T rho, int MP, int npanel, T* w) {
+    const int64_t vecs = (int64_t)npanel * MP * 16 / VecOf<T>::N;
+    if (vecs <= 0) return;
+    const dim3 grid((unsigned)((vecs + 255) / 256)), block(256);
+    if (rho_row) hipLaunchKernelGGL((k_panel_w<T, true>), grid, block, 0, st, z, y, active, rho_row, rho, MP, vecs, w);
+    else hipLaunchKernelGGL((k_panel_w<T, false>), grid, block, 0, st, z, y, active, rho_row, rho, MP, vecs, w);
+}
+
 template <typename T> void scale_rows(hipStream_t st, const T* src, const T* scale, int rows, int cols, T* dst) {
     const int vpr = cols / VecOf<T>::N;
     const int64_t vecs = (int64_t)rows * vpr;
@@ -389,6 +420,7 @@ template <typename T> void scale_rows(hipStream_t st, const T* src, const T* sca
 
 #define INST(T)                                                                                                                         \
     template void scale_rows<T>(hipStream_t, const T*, const T*, int, int, T*);                                                         \
+    template void panel_w<T>(hipStream_t, const T*, const T*, const int*, const T*, T, int, int, T*);                                   \
     template void shared_panel<T>(hipStream_t, SharedPanelOp, const PanelArgs<T>&);                                                     \
     template void shared_check<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,     \
                                   const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double);        \

@@ -552,7 +552,30 @@ struct BatchSolverBase {
     virtual bool update_vectors(const double* q, const double* l, const double* u) { (void)q; (void)l; (void)u; return false; }   // shared-matrix batches only
     virtual bool takes_rho_scale() const { return false; }                            // shared-matrix batches only
     virtual void set_rho_scale(const double* scale) { (void)scale; }                  // scale: [m] validated by the caller, or NULL
+    virtual bool takes_family_rho() const { return false; }                           // shared-matrix batches only: one factor, hence one rho to move
+    int family_rho = 0;                                                               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule below
 };
+
+// Family-wide adaptive rho of the shared-matrix batches (qps_set_shared_adaptive_rho): the proposal of SolveQuadraticProgram.jl:92-96 with the four norms taken from
+// the worst columns still running after this check -- bp = argmax normResPrim / maxNormPrim, bd = argmax normResDual / maxNormDual (lowest index on ties, a NaN
+// quotient never wins against a number).  res: 8 doubles per column as k_shared_decide leaves them ([0..3] the four norms).  No running column: rhorho stays.
+// With one column this is k_check_decide's expression; a NaN proposal stays NaN and never passes the switch test of :47.
+inline double family_rho_proposal(const double* res, const std::vector<int>& active, int count, double rho, double rhorho) {
+    int bp = -1, bd = -1; double qp = 0, qd = 0;
+    for (int b = 0; b < count; ++b) {
+        if (!active[b]) continue;
+        const double* r = res + 8 * b;
+        const double p = r[0] / r[2], d = r[1] / r[3];
+        if (bp < 0 || (std::isnan(qp) && !std::isnan(p)) || p > qp) { bp = b; qp = p; }
+        if (bd < 0 || (std::isnan(qd) && !std::isnan(d)) || d > qd) { bd = b; qd = d; }
+    }
+    if (bp < 0) return rhorho;
+    const double MIN_VAL_RHO = 1e-3, MAX_VAL_RHO = 1e6;                                     // :81-82
+    const double numeratorVal = res[8 * bp + 0] * res[8 * bd + 3];                          // normResPrim_bp * maxNormDual_bd
+    const double denominatorVal = res[8 * bd + 1] * res[8 * bp + 2];                        // normResDual_bd * maxNormPrim_bp
+    const double t = rho * std::sqrt(numeratorVal / denominatorVal);
+    return t > MAX_VAL_RHO ? MAX_VAL_RHO : (t < MIN_VAL_RHO ? MIN_VAL_RHO : t);
+}
 
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
     StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
@@ -810,7 +833,7 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
 // path, a scenario sweep).  One copy of every matrix, one factorisation, one sweep matrix with a single inverted block; the state lives in
 // 16-column panels and every product of the loop is a row-major matrix times panels on the MFMA pipe (k_shared.hip), so a matrix is read once
 // per launch whatever `count` is.  Per iteration: A' (a row-major copy of the transpose), the lower and the upper triangle of S, A.
-// rho is fixed (a common factor needs a common rho); every column keeps its own check, flag, stopping iteration and residuals, and a column
+// rho is common (a common factor needs a common rho): fixed, or moved for the whole family by qps_set_shared_adaptive_rho; every column keeps its own check, flag, stopping iteration and residuals, and a column
 // that stopped is frozen by the active mask, exactly as BatchedDenseSolver does.
 // =================================================================================================================
 template <typename T> inline int shared_batch_max_np() { return 16 * 512 * VecOf<T>::N; }   // whole-factor explicit inverse: 16384 fp64 / 32768 fp32 (k_trsv.hip)
@@ -824,7 +847,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
     int* fail = nullptr; int* d_active = nullptr; int* h_int = nullptr;
     unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
     bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0;
+    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0, cat_fac = 0, cat_switch = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
     // Per-row rho scale (qps_set_shared_rho_scale): row i runs with rho_i = rho s_i.  Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so
     // M = PI + rho Ws'Ws comes out of the same symmetric product and a change of the base rho alone only re-assembles; rs_rho / rs_rho1 hold rho_i and 1 / rho_i
@@ -854,6 +877,8 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         cat_bwd = prof.category("shared: backward sweep + x (MFMA panels)", s * ((double)n * (n + 1) / 2 + 5.0 * c * n));
         cat_pass = prof.category("shared: A x~ + row updates (MFMA panels)", s * ((double)m * n + c * (n + 8.0 * m)));
         cat_chk = prof.category("shared: check (A x, P x, A'y, norms)", s * (2.0 * m * n + (double)n * n + c * (8.0 * n + 6.0 * m)));
+        cat_fac = prof.category("shared: factorisation at setup", s * ((double)m * n + 4.0 * n * n));
+        cat_switch = prof.category("shared: rho switch (assemble, Cholesky, w)", s * (3.0 * n * n + 3.0 * c * m));
     }
     ~SharedBatchSolver() override {
         (void)hipSetDevice(device);
@@ -892,6 +917,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         if (yh) get_panels(y, yh, m, MP);
     }
     bool takes_rho_scale() const override { return true; }
+    bool takes_family_rho() const override { return true; }
     void set_rho_scale(const double* s) override {
         HIPC(hipSetDevice(device));
         HIPC(hipStreamSynchronize(st));
@@ -942,18 +968,21 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
 
     void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
         HIPC(hipSetDevice(device));
-        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: adptRho is not supported (one factor serves every column, so rho is common and fixed)");
+        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: adptRho is not supported (one factor serves every column, so the per-problem rule cannot run; "
+                                                           "qps_set_shared_adaptive_rho turns on the family-wide rule)");
         if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: polishing is not supported");
         if (p.trsvBlock != 0 && p.trsvBlock < n)
             throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: trsvBlock must be 0 or >= n (the sweeps run over one inverted block covering the whole factor)");
         if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: QPS_LINSYS_CHOLESKY only");
         const double t0 = now_s();
-        const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
+        if (family_rho && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
+        double rho = p.rho, rhorho = rho;                                                           // :43; rho moves under the family rule only
+        const double sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
         const bool scaled = !rho_scale.empty();
         if (scaled) push_row_rho(rho);
-        if (!reuse) factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma);        // :36
+        if (!reuse) { ProfScope ps(prof, cat_fac, 1); factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma); }   // :36
         put_panels(xh, x, n, NP);
         for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
         for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st));     // :39-41
@@ -976,7 +1005,22 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         const SharedPanelOp op_row = scaled ? SharedPanelOp::rows_zy_scaled : SharedPanelOp::rows_zy;
         const PanelArgs<T> a_ax = product_args(A, NP, MP, NP, x, Ax), a_px = product_args(P, NP, NP, NP, x, Px), a_aty = product_args(At, MP, NP, MP, y, Aty);
         int nactive = count;
+        std::vector<int> nref(count, 0); std::vector<double> rho_col(count, rho), prop_col(count, rho); double tref = 0;
         for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
+            if (family_rho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {         // :47, once for the family
+                const double ta = now_s();
+                {
+                    ProfScope ps(prof, cat_switch, 1);
+                    rho = rhorho;
+                    factorize(rho, sigma, false);                                                   // changedΡ: A'A is kept, assembly and Cholesky only
+                    if (scaled) push_row_rho(rho);
+                    a_row.rho = (T)rho;
+                    panel_w<T>(st, z, y, d_active, scaled ? rs_rho : nullptr, (T)rho, MP, npanel, w);   // w held rho z - y of the previous rho
+                }
+                for (int b = 0; b < count; ++b) if (active[b]) { ++nref[b]; rho_col[b] = rho; }
+                HIPC(hipStreamSynchronize(st));                                                     // tRefactor: host wall time until the device has finished the switch
+                tref += now_s() - ta;
+            }
             const int lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one launch of each kernel in 50 iterations
             { ProfLaunchScope ps(prof, cat_atw, lvl); shared_panel<T>(st, SharedPanelOp::rhs, a_rhs); }          // LinearSystemSolvers.jl:134-136
             { ProfLaunchScope ps(prof, cat_fwd, lvl); shared_panel<T>(st, SharedPanelOp::forward, a_fwd); }      // :137, L y = t
@@ -1001,6 +1045,10 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
                 resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
                 if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
             }
+            if (family_rho) {
+                rhorho = family_rho_proposal(res_host, active, count, rho, rhorho);
+                for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = rhorho;
+            }
             if (any_done && nactive > 0) push_active();
         }
         HIPC(hipStreamSynchronize(st));
@@ -1009,9 +1057,9 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         get_panels(x, xh, n, NP);
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
-            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = 0; in.cgIterations = 0;
-            in.rhoFinal = rho; in.rhoProposed = rho; in.resPrim = resP[b]; in.resDual = resD[b];
-            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = 0;   // wall time of the whole batch
+            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
+            in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
+            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
             in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
             in.trsvBlock = nb; in.sweepVariant = 3; in.sweepGaveUp = 0; in.cgExplicit = 0;
         }
@@ -1023,7 +1071,8 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
 // The linear system is the sparse L D L' of the KKT matrix (k_ldl.hip): ordering and symbolic factor once at creation (host only), ONE numeric
 // factorisation per (rho, sigma), and every iteration runs the level-scheduled sweeps on 16-column panels -- the index and value of a factor entry are
 // loaded once for 16 QPs, the launch chain is paid once per batch.  The check's A x, P x, A'y are CSR x panel products (k_csr_panel.hip).
-// rho is fixed; every column keeps its own check, flag, stopping iteration and residuals and is frozen by the active mask, as in SharedBatchSolver.
+// rho is common: fixed, or moved for the whole family (qps_set_shared_adaptive_rho); every column keeps its own check, flag, stopping iteration and residuals and
+// is frozen by the active mask, as in SharedBatchSolver.
 // =================================================================================================================
 struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
     LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;
@@ -1037,7 +1086,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     int* d_active = nullptr; int* h_int = nullptr;
     unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
     bool factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    LdlPanelProf pf; int cat_chk = 0;
+    LdlPanelProf pf; int cat_chk = 0, cat_fac = 0, cat_switch = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
     // Per-row rho scale (qps_set_shared_rho_scale): rho_i = rho s_i and 1 / rho_i by the caller's row (m long), formed in double and rounded once, for the base
     // rho rs_base (0: stale); the factor object reads them in its numeric factorisation and panel kernels.  They exist only while a scale is set.
@@ -1075,6 +1124,8 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         pf.cat_bwd = prof.category("sparse shared: backward levels (panels)", np * ents * (s + 4) + s * c * (ents + 3.0 * Ns));
         pf.cat_post = prof.category("sparse shared: post + update (panels)", 4.0 * Nd * np + s * c * (2.0 * Nd + 5.0 * n + 8.0 * m));
         cat_chk = prof.category("sparse shared: check (A x, P x, A'y, norms)", np * (2.0 * annz + pnnz) * (s + 4) + s * c * ((2.0 * annz + pnnz) + 8.0 * n + 6.0 * m));
+        cat_fac = prof.category("sparse shared: factorisation at setup", (s + 4) * ents + s * (pnnz + annz));
+        cat_switch = prof.category("sparse shared: rho switch (numeric L D L')", (s + 4) * ents + s * (pnnz + annz));
         update_vectors(qh, lh, uh);
     }
     ~SparseSharedBatchSolver() override {
@@ -1116,6 +1167,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         if (yh) get_panels(y, yh, m);
     }
     bool takes_rho_scale() const override { return true; }
+    bool takes_family_rho() const override { return true; }
     void set_rho_scale(const double* s) override {
         HIPC(hipSetDevice(device));
         HIPC(hipStreamSynchronize(st));
@@ -1142,15 +1194,19 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     }
     void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
         HIPC(hipSetDevice(device));
-        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: adptRho is not supported (one factor serves every column, so rho is common and fixed)");
+        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: adptRho is not supported (one factor serves every column, so the per-problem rule cannot "
+                                                           "run; qps_set_shared_adaptive_rho turns on the family-wide rule)");
         if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: polish is not supported");
         if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_KKT_LDL) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: linsys must be QPS_LINSYS_AUTO or QPS_LINSYS_KKT_LDL");
         const double t0 = now_s();
-        const double rho = p.rho, sigma = p.sigma, alpha = p.alpha;
+        if (family_rho && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
+        double rho = p.rho, rhorho = rho;                                                           // :43; rho moves under the family rule only
+        const double sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
         if (!rho_scale.empty()) push_row_rho(rho);
         if (!reuse) {                                                                               // :36: numeric factorisation, once for all columns
+            ProfScope ps(prof, cat_fac, 1);
             factor_valid = false;
             ++num_factorizations;
             ldl->factorize(rho, sigma);
@@ -1171,7 +1227,24 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         const double t1 = now_s();
         LdlPanelState<T> s; s.x = x; s.xp = xp; s.q = q; s.z = z; s.zp = zp; s.y = y; s.l = l; s.u = u; s.active = d_active; s.npanel = npanel;
         int nactive = count; bool rhs_ready = false;
+        std::vector<int> nref(count, 0); std::vector<double> rho_col(count, rho), prop_col(count, rho); double tref = 0;
         for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
+            if (family_rho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {         // :47, once for the family
+                const double ta = now_s();
+                {
+                    ProfScope ps(prof, cat_switch, 1);
+                    rho = rhorho;
+                    if (!rho_scale.empty()) push_row_rho(rho);                                      // the numeric factorisation reads rho_i
+                    factor_valid = false;
+                    ++num_factorizations;
+                    ldl->factorize(rho, sigma);                                                     // changedΡ: numeric only, on the frozen pattern
+                    factor_valid = true; fac_rho = rho;
+                    rhs_ready = false;                                                              // the right-hand side left behind holds 1 / rho of the previous rho
+                }
+                for (int b = 0; b < count; ++b) if (active[b]) { ++nref[b]; rho_col[b] = rho; }
+                HIPC(hipStreamSynchronize(st));                                                     // tRefactor: host wall time until the device has finished the switch
+                tref += now_s() - ta;
+            }
             pf.lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one sample of each category in 50 iterations
             ldl->iterate_panels(s, alpha, rho, sigma, rhs_ready, pf);                               // LinearSystemSolvers.jl:37-40, SolveQuadraticProgram.jl:56-61
             rhs_ready = true;
@@ -1194,6 +1267,10 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
                 resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
                 if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
             }
+            if (family_rho) {
+                rhorho = family_rho_proposal(res_host, active, count, rho, rhorho);
+                for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = rhorho;
+            }
             if (any_done && nactive > 0) push_active();
         }
         HIPC(hipStreamSynchronize(st));
@@ -1202,9 +1279,9 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         get_panels(x, xh, n);
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
-            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = 0; in.cgIterations = 0;
-            in.rhoFinal = rho; in.rhoProposed = rho; in.resPrim = resP[b]; in.resDual = resD[b];
-            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = 0;   // wall time of the whole batch
+            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
+            in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
+            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
             in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
             in.trsvBlock = 0; in.sweepVariant = 0; in.sweepGaveUp = 0; in.cgExplicit = 0;
         }
@@ -1643,6 +1720,16 @@ QPS_API int32_t qps_set_shared_rho_scale(qps_handle hh, const double* scale) {
             return fail_with(h, QPS_ERR_BAD_ARGUMENT, b);
         }
     return guarded(h, [&] { h->fused_batch->set_rho_scale(scale); });
+}
+
+QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (mode != 0 && mode != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_adaptive_rho: mode must be 0 (fixed rho) or 1 (family-wide adaptive rho)");
+    const char* other = "qps_set_shared_adaptive_rho: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) run the family-wide rho rule";
+    if (!h->fused_batch || !h->fused_batch->takes_family_rho()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    h->fused_batch->family_rho = mode;
+    return QPS_OK;
 }
 
 QPS_API int32_t qps_solve_batch_multi(int64_t count, int64_t n, int64_t m, const double* P, const double* A, const double* q, const double* l, const double* u,

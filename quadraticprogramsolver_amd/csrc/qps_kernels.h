@@ -163,6 +163,9 @@ template <typename T> void from_panels(hipStream_t st, const T* src, int count, 
 template <typename T> void transpose_rowmajor(hipStream_t st, const T* src, int64_t lds, int rows, int cols, T* dst, int64_t ldd);   // dims multiples of 32
 // dst[r][c] = scale[r] * src[r][c] for a row-major rows x cols matrix (ld = cols, a multiple of VecOf<T>::N): W = diag(sqrt(s_i)) A of the per-row rho scale
 template <typename T> void scale_rows(hipStream_t st, const T* src, const T* scale, int rows, int cols, T* dst);
+// w = rho z - y over panels [npanel][MP][16] for the columns of the active mask (rho_row != NULL: rho_i of the row instead of rho): what the rows_zy / rows_zy_scaled
+// epilogue leaves behind, re-formed after a switch of the family rho (qps_set_shared_adaptive_rho)
+template <typename T> void panel_w(hipStream_t st, const T* z, const T* y, const int* active, const T* rho_row, T rho, int MP, int npanel, T* w);
 
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);

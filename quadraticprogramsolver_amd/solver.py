@@ -293,7 +293,8 @@ class QuadraticProgramSharedBatch(_Handle):
     """``count`` QPs on ONE ``mP`` and ONE ``mA`` that differ in ``q``, ``l`` and ``u`` only (qps_create_dense_shared_batch): an MPC horizon
     re-solved every sample, a regularisation path, a scenario sweep.  ``mQ`` is [count x n], ``mL`` / ``mU`` are [count x m].  The matrices are
     stored, factorised and streamed once for all columns; every column keeps its own check, flag, stopping iteration and residuals, exactly as if
-    solved alone with a fixed ρ (``adptΡ``, ``polish`` and a ``trsvBlock`` below n are refused with QPS_ERR_UNSUPPORTED)."""
+    solved alone with a fixed ρ (``adptΡ``, ``polish`` and a ``trsvBlock`` below n are refused with QPS_ERR_UNSUPPORTED); ``set_adaptive_rho`` lets one ρ adapt
+    for the whole family."""
 
     def __init__(self, mP, mA, mQ, mL, mU, *, dtype="f64", device=0):
         dense = lambda M: np.asarray(M.toarray() if sp.issparse(M) else M, dtype=np.float64)
@@ -336,6 +337,14 @@ class QuadraticProgramSharedBatch(_Handle):
         factorises, also with ``reuseFactor=True``; ``ρ`` of ``solve`` stays the base value."""
         s = None if vS is None else _vec(vS, "vS", self.m)
         _lib.check(_lib.lib().qps_set_shared_rho_scale(self._h, None if s is None else _dp(s)), self._h)
+
+    def set_adaptive_rho(self, on=True):
+        """Family-wide adaptive ρ (qps_set_shared_adaptive_rho): ONE ρ that moves for all columns by the reference's rule, with the norms of the worst
+        columns still running; a switch re-factorises once for the whole batch and uses ``fctrΡ`` of ``solve``.  ``False`` goes back to the fixed ρ.
+        The setting stays with the handle.  Per column, ``numRefactor`` / ``rhoFinal`` / ``rhoProposed`` / ``tRefactor`` of the info dicts report it;
+        ``solve(reuseFactor=True, ρ=rhoFinal)`` of the column that ran longest re-solves without factorising.  ``adptΡ=True`` (the per-problem rule)
+        stays refused."""
+        _lib.check(_lib.lib().qps_set_shared_adaptive_rho(self._h, 1 if on else 0), self._h)
 
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
