@@ -262,6 +262,31 @@ int32_t qps_set_shared_rho_scale(qps_handle h, const double *scale /* [m]; NULL 
  * not a shared-matrix batch. */
 int32_t qps_set_shared_adaptive_rho(qps_handle h, int32_t mode /* 0 fixed rho, 1 family-wide rule */);
 
+/* Ruiz equilibration of a shared-matrix batch handle (dense or sparse; section 5.1 of the OSQP paper, item 2 of the reference's to-do list), opt-in: passes = 0
+ * (the default) leaves the handle exactly as it is, passes = 1..50 runs that many passes.  The scaling D = diag(2^kd) of the variables and E = diag(2^ke) of the
+ * constraints depends on P and A only, so it is computed once for the family and serves every column and every re-solve after qps_update_shared_vectors.  D and E
+ * are exact powers of two: scaling and unscaling never round, the exponents are integer arithmetic (the device and a numpy restatement agree exactly), and clearing
+ * the option restores the matrices bit for bit -- no second copy of a matrix is kept.
+ * The rule: kd = ke = 0; one pass is Jacobi, with all norms taken through the exponents from before the pass,
+ *   cn_j = max(max_i |P_ij| 2^(kd_i + kd_j), max_i |A_ij| 2^(ke_i + kd_j)),   rn_i = max_j |A_ij| 2^(ke_i + kd_j),
+ * formed in double from the entries as stored in the handle's type (an fp32 handle scales the fp32-rounded matrices).  For a norm v = f 2^e > 0, f in [0.5, 1), the
+ * step is -floor(e / 2) -- the power of two nearest to 1 / sqrt(v) on a log scale -- and 0 for v = 0 (an empty row or column); then kd_j = clamp(kd_j + step(cn_j),
+ * -13, 13), likewise ke (OSQP's [1e-4, 1e4]).  OSQP's cost scaling c is not applied: it depends on q, which differs per column, and it would scale P.
+ * The loop then runs unchanged on D P D, E A D, D q, E l, E u; in the caller's variables that is the ADMM loop with sigma_j = sigma / D_j^2 and rho_i = rho E_i^2,
+ * so the iterates differ from those of an unscaled solve.  The warm start goes in as D^-1 x, the result comes back as D x~, qps_get_dual returns E^-1 z~ and E y~, and
+ * the convergence check -- hence resPrim / resDual, the per-column flags and the family-wide rho rule -- sees the unscaled norms, as in OSQP.  With a rho scale set,
+ * row i runs with rho * scale[i] on the scaled rows.  adptRho and polish stay refused.
+ * Range: after the passes and before anything is modified, the largest and the smallest non-zero scaled matrix magnitude have to be normal numbers of the handle's
+ * type (this matters for fp32); otherwise QPS_ERR_UNSUPPORTED and the handle stays as it was.  Vector entries are not range-checked: a scaled bound that overflows
+ * is a bound at infinity.
+ * Setting, changing or clearing invalidates the factorisation: the next qps_solve_batch factorises even with reuseFactor = 1.  While the option is on the handle
+ * keeps two int vectors (n and m) on the device.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle or passes outside 0..50 (before a device is needed; the handle keeps its state).  QPS_ERR_UNSUPPORTED (qps_last_error names
+ * the reason): any handle that is not a shared-matrix batch, or the range check above.
+ * qps_get_shared_equilibration writes D ([n]) and E ([m]) as doubles, all ones while the option is off; either pointer may be NULL. */
+int32_t qps_set_shared_equilibration(qps_handle h, int32_t passes /* 0 = off (default); 1..50 = that many Ruiz passes */);
+int32_t qps_get_shared_equilibration(qps_handle h, double *d_out /* [n] or NULL */, double *e_out /* [m] or NULL */);
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads

@@ -414,6 +414,23 @@ function SharedBatchSetAdaptiveRho!(sb::SharedBatchHip, on::Bool = true)
     return nothing
 end
 
+# Ruiz equilibration with exact powers of two (qps_set_shared_equilibration; OSQP §5.1), opt-in: passes = 1..50 passes of the rule, computed once for the family
+# from mP and mA; 0 or nothing switches it off and restores the matrices bit for bit.  Warm starts, results, duals and the convergence check stay in the caller's
+# units.  Setting, changing or clearing makes the next SharedBatchSolve! factorise, also with reuseFactor = true.
+function SharedBatchSetEquilibration!(sb::SharedBatchHip, passes::Union{Nothing, Integer} = 10)
+    h = sb.h
+    _check(ccall((:qps_set_shared_equilibration, LIBQPS), Int32, (Ptr{Cvoid}, Int32), h, passes === nothing ? 0 : passes), h)
+    return nothing
+end
+
+# (vD [n], vE [m]) of SharedBatchSetEquilibration!: powers of two, all ones while it is off (qps_get_shared_equilibration)
+function SharedBatchEquilibration(sb::SharedBatchHip)
+    h = sb.h
+    vD = zeros(sb.n); vE = zeros(sb.m)
+    GC.@preserve vD vE _check(ccall((:qps_get_shared_equilibration, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h, pointer(vD), pointer(vE)), h)
+    return vD, vE
+end
+
 # factor on the rows that are equalities (l == u) in every column of mL / mU (m x count), 1 elsewhere
 EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
 

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "qps_kernels.h"
+#include "wave_reduce.h"
 
 namespace qps {
 
@@ -226,10 +227,14 @@ __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
 
 // CheckConvergence (SolveQuadraticProgram.jl:79-112), per column: the nine inf-norms of k_check_norms over panels.
 // slots (16 per column): 0 ||Ax-z|| 1 ||Px+q+A'y|| 2 ||Ax|| 3 ||z|| 4 ||Px|| 5 ||A'y|| 6 ||q|| 7 ||x-xp|| 8 ||z-zp||
-template <typename T>
-__global__ __launch_bounds__(256) void k_shared_norms(int n, int m, int NP, int MP, const T* __restrict__ Ax, const T* __restrict__ Px, const T* __restrict__ Aty,
-                                                      const T* __restrict__ q, const T* __restrict__ x, const T* __restrict__ xp, const T* __restrict__ z,
-                                                      const T* __restrict__ zp, unsigned long long* __restrict__ slots) {
+// EQ (qps_set_shared_equilibration): the panels hold the scaled iterates; every term goes back to the caller's units before its norm is taken (OSQP 5.1) --
+// E^-1 on the m-rows, D^-1 on P x, q, A'y and their sum, D on x - xp, with D_j = 2^kd[j], E_i = 2^ke[i].  Differences are formed in T as without the
+// scaling, then moved by the power of two in double (exact).
+template <typename T, bool EQ>
+__device__ __forceinline__ void shared_norms_body(int n, int m, int NP, int MP, const T* __restrict__ Ax, const T* __restrict__ Px, const T* __restrict__ Aty,
+                                                  const T* __restrict__ q, const T* __restrict__ x, const T* __restrict__ xp, const T* __restrict__ z,
+                                                  const T* __restrict__ zp, unsigned long long* __restrict__ slots, const int* __restrict__ kd,
+                                                  const int* __restrict__ ke) {
     const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4;
     const int64_t on = (int64_t)P * NP * 16 + col, om = (int64_t)P * MP * 16 + col;
     unsigned long long v[9];
@@ -238,18 +243,22 @@ __global__ __launch_bounds__(256) void k_shared_norms(int n, int m, int NP, int 
     for (int r = blockIdx.x * 16 + rl; r < max(n, m); r += gridDim.x * 16) {
         if (r < m) {
             const int64_t i = om + (int64_t)r * 16;
-            v[0] = sh_umax(v[0], sh_absbits((double)(Ax[i] - z[i])));   // differences are formed in T (k_loop.hip)
-            v[2] = sh_umax(v[2], sh_absbits((double)Ax[i]));
-            v[3] = sh_umax(v[3], sh_absbits((double)z[i]));
-            v[8] = sh_umax(v[8], sh_absbits((double)(z[i] - zp[i])));
+            const int s = EQ ? -ke[r] : 0;
+            auto nrm = [&](T t) { return sh_absbits(EQ ? ldexp((double)t, s) : (double)t); };
+            v[0] = sh_umax(v[0], nrm(Ax[i] - z[i]));   // differences are formed in T (k_loop.hip)
+            v[2] = sh_umax(v[2], nrm(Ax[i]));
+            v[3] = sh_umax(v[3], nrm(z[i]));
+            v[8] = sh_umax(v[8], nrm(z[i] - zp[i]));
         }
         if (r < n) {
             const int64_t i = on + (int64_t)r * 16;
-            v[1] = sh_umax(v[1], sh_absbits((double)(Px[i] + q[i] + Aty[i])));
-            v[4] = sh_umax(v[4], sh_absbits((double)Px[i]));
-            v[5] = sh_umax(v[5], sh_absbits((double)Aty[i]));
-            v[6] = sh_umax(v[6], sh_absbits((double)q[i]));
-            v[7] = sh_umax(v[7], sh_absbits((double)(x[i] - xp[i])));
+            const int s = EQ ? -kd[r] : 0;
+            auto nrm = [&](T t) { return sh_absbits(EQ ? ldexp((double)t, s) : (double)t); };
+            v[1] = sh_umax(v[1], nrm(Px[i] + q[i] + Aty[i]));
+            v[4] = sh_umax(v[4], nrm(Px[i]));
+            v[5] = sh_umax(v[5], nrm(Aty[i]));
+            v[6] = sh_umax(v[6], nrm(q[i]));
+            v[7] = sh_umax(v[7], sh_absbits(EQ ? ldexp((double)(x[i] - xp[i]), -s) : (double)(x[i] - xp[i])));
         }
     }
 #pragma unroll
@@ -258,6 +267,103 @@ __global__ __launch_bounds__(256) void k_shared_norms(int n, int m, int NP, int 
         v[k] = sh_umax(v[k], __shfl_xor(v[k], 32));
         if ((threadIdx.x & 63) < 16 && v[k] != 0ull) atomicMax(&slots[(int64_t)(P * 16 + col) * 16 + k], v[k]);
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_shared_norms(int n, int m, int NP, int MP, const T* __restrict__ Ax, const T* __restrict__ Px, const T* __restrict__ Aty,
+                                                      const T* __restrict__ q, const T* __restrict__ x, const T* __restrict__ xp, const T* __restrict__ z,
+                                                      const T* __restrict__ zp, unsigned long long* __restrict__ slots) {
+    shared_norms_body<T, false>(n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots, nullptr, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_shared_norms_equil(int n, int m, int NP, int MP, const T* __restrict__ Ax, const T* __restrict__ Px,
+                                                            const T* __restrict__ Aty, const T* __restrict__ q, const T* __restrict__ x, const T* __restrict__ xp,
+                                                            const T* __restrict__ z, const T* __restrict__ zp, unsigned long long* __restrict__ slots,
+                                                            const int* __restrict__ kd, const int* __restrict__ ke) {
+    shared_norms_body<T, true>(n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots, kd, ke);
+}
+
+// ---- Ruiz equilibration with exact powers of two (qps_set_shared_equilibration) ------------------------------------------------------------------------------
+__device__ __forceinline__ double eq_ldexp(double v, int k) { return ldexp(v, k); }
+__device__ __forceinline__ float eq_ldexp(float v, int k) { return ldexpf(v, k); }
+
+// out[r] = 2^kr[r] max_c |M[r][c]| 2^kc[c] in double for a row-major rows x K matrix (ld = K, a multiple of 64): one wave per row, 16 bytes per lane and load,
+// the wave's maximum on the VALU (wave_reduce.h).  Every norm is one wave's own reduction: no atomics, nothing crosses a workgroup, the result does not depend
+// on the launch geometry.  The matrix is read through the exponents and never rewritten between passes (a power of two moves a double exactly).
+// RANGE: also lo[r] = the smallest non-zero scaled magnitude of the row (+Inf for an empty row), for the range check before the matrices are touched.
+template <typename T, bool RANGE>
+__global__ __launch_bounds__(256) void k_equil_rownorm(const T* __restrict__ M, int rows, int K, const int* __restrict__ kr, const int* __restrict__ kc,
+                                                       double* __restrict__ out, double* __restrict__ lo) {
+    constexpr int VN = VecOf<T>::N;
+    typedef T NV __attribute__((ext_vector_type(VN)));
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;                                         // wave-uniform
+    const T* row = M + (int64_t)r * K;
+    double hi = 0.0, mn = INFINITY;
+    for (int c = lane * VN; c < K; c += 64 * VN) {                 // K is a multiple of 64, hence of VN: c < K means c + VN <= K
+        const NV a = *reinterpret_cast<const NV*>(row + c);
+#pragma unroll
+        for (int j = 0; j < VN; ++j) {
+            const double s = ldexp(fabs((double)a[j]), kc[c + j]);
+            hi = fmax(hi, s);
+            if (RANGE && s > 0.0) mn = fmin(mn, s);
+        }
+    }
+    hi = wave_max_all_nonneg(hi);
+    if (RANGE) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o));
+    }
+    if (lane == 0) {
+        out[r] = ldexp(hi, kr[r]);
+        if (RANGE) lo[r] = ldexp(mn, kr[r]);
+    }
+}
+
+// k[i] = clamp(k[i] + step(max(a[i], b[i])), -13, 13) with step(v) = -floor(e / 2) for v = f 2^e, f in [0.5, 1) -- the power of two nearest to 1 / sqrt(v) on
+// a log scale -- and step(0) = 0 (an empty or padding row).  b may be NULL.  13: OSQP's [1e-4, 1e4].
+__global__ void k_equil_update(int len, const double* __restrict__ a, const double* __restrict__ b, int* __restrict__ k) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    double v = a[i];
+    if (b) v = fmax(v, b[i]);
+    int step = 0;
+    if (v > 0.0) { int e; (void)frexp(v, &e); step = -(e >> 1); }   // >> on a negative int: arithmetic, i.e. floor
+    k[i] = max(-13, min(13, k[i] + step));
+}
+
+// M[r][c] *= 2^(sign (kr[r] + kc[c])) in place, 16 bytes per lane (rows x cols, ld = cols, a multiple of VN)
+template <typename T>
+__global__ __launch_bounds__(256) void k_scale_two_sided(T* __restrict__ M, int64_t vecs, int vpr, const int* __restrict__ kr, const int* __restrict__ kc, int sign) {
+    constexpr int VN = VecOf<T>::N;
+    typedef T NV __attribute__((ext_vector_type(VN)));
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= vecs) return;
+    const int r = (int)(i / vpr), c = (int)(i % vpr) * VN, er = kr[r];
+    NV a = reinterpret_cast<NV*>(M)[i];
+#pragma unroll
+    for (int j = 0; j < VN; ++j) a[j] = eq_ldexp(a[j], sign * (er + kc[c + j]));
+    reinterpret_cast<NV*>(M)[i] = a;
+}
+
+// dst[panel][row][16] = src[panel][row][16] 2^(sign k[row]), 16 bytes per lane (VN neighbouring columns of one row); dst may be src.  +-Inf stays +-Inf.
+template <typename T>
+__global__ __launch_bounds__(256) void k_panel_rowscale(const T* src, const int* __restrict__ k, int sign, int rowsP, int64_t vecs, T* dst) {
+    constexpr int VN = VecOf<T>::N;
+    typedef T NV __attribute__((ext_vector_type(VN)));
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= vecs) return;
+    const int e = sign * k[(int)(((i * VN) >> 4) % rowsP)];
+    NV a = reinterpret_cast<const NV*>(src)[i];
+#pragma unroll
+    for (int j = 0; j < VN; ++j) a[j] = eq_ldexp(a[j], e);
+    reinterpret_cast<NV*>(dst)[i] = a;
+}
+
+// v[i] *= 2^(sign e[i]): the value arrays of the sparse handle (the factor's [P; A] values, the CSR copies of the check), exponent per entry from the pattern
+template <typename T>
+__global__ __launch_bounds__(256) void k_scale_entries(T* __restrict__ v, const int* __restrict__ e, int sign, int64_t cnt) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < cnt) v[i] = eq_ldexp(v[i], sign * e[i]);
 }
 
 __device__ __forceinline__ double sh_jmax(double a, double b) { return (isnan(a) || isnan(b)) ? (double)NAN : (a > b ? a : b); }
@@ -383,9 +489,10 @@ void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a) {
 template <typename T>
 void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* Ax, const T* Px, const T* Aty, const T* q, const T* x, const T* xp,
                   const T* z, const T* zp, unsigned long long* slots, double* res_dev, const int* active, double epsAbs, double epsRel, double epsAdmm,
-                  double rho) {
+                  double rho, const int* kd, const int* ke) {
     const int blocks = std::max(1, std::min((std::max(n, m) + 15) / 16, 256));
-    hipLaunchKernelGGL((k_shared_norms<T>), dim3(blocks, npanel), dim3(256), 0, st, n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots);
+    if (kd) hipLaunchKernelGGL((k_shared_norms_equil<T>), dim3(blocks, npanel), dim3(256), 0, st, n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots, kd, ke);
+    else hipLaunchKernelGGL((k_shared_norms<T>), dim3(blocks, npanel), dim3(256), 0, st, n, m, NP, MP, Ax, Px, Aty, q, x, xp, z, zp, slots);
     hipLaunchKernelGGL(k_shared_decide, dim3((npanel * 16 + 63) / 64), dim3(64), 0, st, npanel * 16, slots, res_dev, active, epsAbs, epsRel, epsAdmm, rho);
 }
 
@@ -418,12 +525,42 @@ template <typename T> void scale_rows(hipStream_t st, const T* src, const T* sca
     hipLaunchKernelGGL((k_scale_rows<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, src, scale, vecs, vpr, dst);
 }
 
+template <typename T> void equil_rownorm(hipStream_t st, const T* M, int rows, int K, const int* kr, const int* kc, double* out, double* lo) {
+    if (rows <= 0) return;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    if (lo) hipLaunchKernelGGL((k_equil_rownorm<T, true>), grid, block, 0, st, M, rows, K, kr, kc, out, lo);
+    else hipLaunchKernelGGL((k_equil_rownorm<T, false>), grid, block, 0, st, M, rows, K, kr, kc, out, lo);
+}
+void equil_update(hipStream_t st, int len, const double* a, const double* b, int* k) {
+    if (len > 0) hipLaunchKernelGGL(k_equil_update, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, len, a, b, k);
+}
+template <typename T> void scale_two_sided(hipStream_t st, T* M, int rows, int cols, const int* kr, const int* kc, int sign) {
+    const int vpr = cols / VecOf<T>::N;
+    const int64_t vecs = (int64_t)rows * vpr;
+    if (vecs <= 0) return;
+    hipLaunchKernelGGL((k_scale_two_sided<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, M, vecs, vpr, kr, kc, sign);
+}
+template <typename T> void panel_rowscale(hipStream_t st, const T* src, const int* k, int sign, int rowsP, int npanel, T* dst) {
+    const int64_t vecs = (int64_t)npanel * rowsP * 16 / VecOf<T>::N;
+    if (vecs <= 0) return;
+    hipLaunchKernelGGL((k_panel_rowscale<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, src, k, sign, rowsP, vecs, dst);
+}
+template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int sign, int64_t cnt) {
+    if (cnt <= 0) return;
+    hipLaunchKernelGGL((k_scale_entries<T>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, v, e, sign, cnt);
+}
+
 #define INST(T)                                                                                                                         \
+    template void equil_rownorm<T>(hipStream_t, const T*, int, int, const int*, const int*, double*, double*);                          \
+    template void scale_two_sided<T>(hipStream_t, T*, int, int, const int*, const int*, int);                                           \
+    template void panel_rowscale<T>(hipStream_t, const T*, const int*, int, int, int, T*);                                              \
+    template void scale_entries<T>(hipStream_t, T*, const int*, int, int64_t);                                                          \
     template void scale_rows<T>(hipStream_t, const T*, const T*, int, int, T*);                                                         \
     template void panel_w<T>(hipStream_t, const T*, const T*, const int*, const T*, T, int, int, T*);                                   \
     template void shared_panel<T>(hipStream_t, SharedPanelOp, const PanelArgs<T>&);                                                     \
     template void shared_check<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,     \
-                                  const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double);        \
+                                  const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double,          \
+                                  const int*, const int*);                                                                              \
     template void to_panels<T>(hipStream_t, const double*, int, int, int, T*);                                                          \
     template void from_panels<T>(hipStream_t, const T*, int, int, int, double*);                                                        \
     template void transpose_rowmajor<T>(hipStream_t, const T*, int64_t, int, int, T*, int64_t);

@@ -5,6 +5,7 @@
 // There is NO CPU fallback: without a HIP device every entry point fails with QPS_ERR_NO_DEVICE.
 #include "ldl_symbolic.h"
 #include <atomic>
+#include <limits>
 #include <memory>
 #include <thread>
 
@@ -554,7 +555,28 @@ struct BatchSolverBase {
     virtual void set_rho_scale(const double* scale) { (void)scale; }                  // scale: [m] validated by the caller, or NULL
     virtual bool takes_family_rho() const { return false; }                           // shared-matrix batches only: one factor, hence one rho to move
     int family_rho = 0;                                                               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule below
+    virtual bool takes_equilibration() const { return false; }                        // shared-matrix batches only
+    virtual void set_equilibration(int passes) { (void)passes; }                      // passes: 0..50 validated by the caller
+    std::vector<int> eq_kd, eq_ke;                                                    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
 };
+
+// Ruiz equilibration of the shared-matrix batches with exact powers of two (qps_set_shared_equilibration).  The step for a norm v = f 2^e, f in [0.5, 1), is
+// -floor(e / 2): the power of two nearest to 1 / sqrt(v) on a log scale; 0 for v = 0.  Exponents stay in [-13, 13] (OSQP's [1e-4, 1e4]).
+constexpr int EQUIL_CLAMP = 13;
+inline int equil_step(double v) {
+    if (!(v > 0.0)) return 0;
+    int e; (void)std::frexp(v, &e);
+    return -(int)std::floor(e / 2.0);
+}
+// the range check: every non-zero scaled matrix entry has to stay a normal number of the handle's type
+template <typename T> inline void equil_check_range(double hi, double lo) {
+    if (hi > (double)std::numeric_limits<T>::max() || lo < (double)std::numeric_limits<T>::min()) {
+        char b[256];
+        snprintf(b, sizeof b, "qps_set_shared_equilibration: a scaled matrix entry would leave the normal range of the handle's type (largest %.3g, smallest non-zero %.3g, "
+                              "range %.3g .. %.3g); the handle is unchanged", hi, lo, (double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max());
+        throw QpsError(QPS_ERR_UNSUPPORTED, b);
+    }
+}
 
 // Family-wide adaptive rho of the shared-matrix batches (qps_set_shared_adaptive_rho): the proposal of SolveQuadraticProgram.jl:92-96 with the four norms taken from
 // the worst columns still running after this check -- bp = argmax normResPrim / maxNormPrim, bd = argmax normResDual / maxNormDual (lowest index on ties, a NaN
@@ -853,6 +875,9 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
     // M = PI + rho Ws'Ws comes out of the same symmetric product and a change of the base rho alone only re-assembles; rs_rho / rs_rho1 hold rho_i and 1 / rho_i
     // (MP long, padding rows: scale 1), formed in double and rounded once, for the base rho rs_base (0: stale).  All four buffers exist only while a scale is set.
     std::vector<double> rho_scale; T *Ws = nullptr, *rs_sqrt = nullptr, *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
+    // Equilibration (qps_set_shared_equilibration): while it is on, P, A, At hold D P D, E A D, D A' E and q, l, u hold D q, E l, E u -- scaled in place by exact
+    // powers of two, undone in place when it is cleared -- and kd / ke (NP / MP ints, padding 0) are the exponents on the device; the loop kernels run as they are.
+    int *kd = nullptr, *ke = nullptr;
 
     SharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_) {
         device = dev; n = n_; m = m_; count = cnt;
@@ -906,15 +931,75 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
     }
     bool update_vectors(const double* qh, const double* lh, const double* uh) override {
         HIPC(hipSetDevice(device));
-        if (qh) put_panels(qh, q, n, NP);
-        if (lh) put_panels(lh, l, m, MP);
-        if (uh) put_panels(uh, u, m, MP);
+        if (qh) { put_panels(qh, q, n, NP); if (kd) panel_rowscale<T>(st, q, kd, 1, NP, npanel, q); }          // q~ = D q
+        if (lh) { put_panels(lh, l, m, MP); if (kd) panel_rowscale<T>(st, l, ke, 1, MP, npanel, l); }          // l~ = E l, u~ = E u (infinite stays infinite)
+        if (uh) { put_panels(uh, u, m, MP); if (kd) panel_rowscale<T>(st, u, ke, 1, MP, npanel, u); }
         return true;   // the factor depends on P, A, rho, sigma only: it stays valid
     }
     void get_dual(double* zh, double* yh) override {
         HIPC(hipSetDevice(device));
-        if (zh) get_panels(z, zh, m, MP);
-        if (yh) get_panels(y, yh, m, MP);
+        if (!kd) {
+            if (zh) get_panels(z, zh, m, MP);
+            if (yh) get_panels(y, yh, m, MP);
+            return;
+        }
+        // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
+        if (zh) { panel_rowscale<T>(st, z, ke, -1, MP, npanel, Ax); get_panels(Ax, zh, m, MP); }
+        if (yh) { panel_rowscale<T>(st, y, ke, 1, MP, npanel, Ax); get_panels(Ax, yh, m, MP); }
+    }
+    bool takes_equilibration() const override { return true; }
+    // the matrices and every vector the handle keeps between calls, in place: *= 2^(+-k) by the exponents in kd / ke
+    void apply_equilibration(int sign) {
+        scale_two_sided<T>(st, P, NP, NP, kd, kd, sign);
+        scale_two_sided<T>(st, A, MP, NP, ke, kd, sign);
+        scale_two_sided<T>(st, At, NP, MP, kd, ke, sign);
+        panel_rowscale<T>(st, q, kd, sign, NP, npanel, q);
+        for (T* v : {l, u, z}) panel_rowscale<T>(st, v, ke, sign, MP, npanel, v);
+        panel_rowscale<T>(st, y, ke, -sign, MP, npanel, y);
+    }
+    void set_equilibration(int passes) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        const bool was_on = kd != nullptr;
+        if (was_on) apply_equilibration(-1);                       // the caller's matrices again, bit for bit
+        int *nkd = nullptr, *nke = nullptr; std::vector<int> hkd, hke;
+        if (passes > 0) {
+            nkd = mem.dalloc<int>(NP, st); nke = mem.dalloc<int>(MP, st);
+            double* nrm = mem.dalloc<double>(3 * (int64_t)NP + 2 * (int64_t)MP, st);
+            double *cnP = nrm, *cnA = nrm + NP, *rn = nrm + 2 * NP, *loP = nrm + 2 * NP + MP, *loA = nrm + 3 * NP + MP;
+            for (int k = 0; k < passes; ++k) {                     // Jacobi: every norm of a pass reads the exponents from before the pass
+                equil_rownorm<T>(st, P, NP, NP, nkd, nkd, cnP, nullptr);        // P is symmetric and At is kept row-major: every norm is a row reduction
+                equil_rownorm<T>(st, At, NP, MP, nkd, nke, cnA, nullptr);
+                equil_rownorm<T>(st, A, MP, NP, nke, nkd, rn, nullptr);
+                equil_update(st, NP, cnP, cnA, nkd);
+                equil_update(st, MP, rn, nullptr, nke);
+            }
+            equil_rownorm<T>(st, P, NP, NP, nkd, nkd, cnP, loP);
+            equil_rownorm<T>(st, A, MP, NP, nke, nkd, rn, loA);
+            std::vector<double> h(3 * (size_t)NP + 2 * (size_t)MP);
+            hkd.resize(NP); hke.resize(MP);
+            HIPC(hipMemcpyAsync(h.data(), nrm, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+            HIPC(hipMemcpyAsync(hkd.data(), nkd, sizeof(int) * NP, hipMemcpyDeviceToHost, st));
+            HIPC(hipMemcpyAsync(hke.data(), nke, sizeof(int) * MP, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            mem.release(nrm);
+            double hi = 0, lo = INFINITY;
+            for (int i = 0; i < NP; ++i) { hi = std::fmax(hi, h[i]); lo = std::fmin(lo, h[2 * (size_t)NP + MP + i]); }
+            for (int i = 0; i < MP; ++i) { hi = std::fmax(hi, h[2 * (size_t)NP + i]); lo = std::fmin(lo, h[3 * (size_t)NP + MP + i]); }
+            try { equil_check_range<T>(hi, lo); }
+            catch (...) {
+                mem.release(nkd); mem.release(nke);
+                if (was_on) { apply_equilibration(1); HIPC(hipStreamSynchronize(st)); }   // the previous scaling, its factor and its cached product stay
+                throw;
+            }
+        }
+        mem.release(kd); mem.release(ke);
+        kd = nkd; ke = nke;
+        eq_kd.assign(hkd.begin(), hkd.begin() + (passes > 0 ? n : 0)); eq_ke.assign(hke.begin(), hke.begin() + (passes > 0 ? m : 0));
+        if (kd) apply_equilibration(1);
+        if (Ws) scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);         // the per-row rho scale reads the new A
+        HIPC(hipStreamSynchronize(st));
+        factor_valid = false; have_AA = false;                     // the cached product and the factor belong to the previous matrices
     }
     bool takes_rho_scale() const override { return true; }
     bool takes_family_rho() const override { return true; }
@@ -984,6 +1069,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         if (scaled) push_row_rho(rho);
         if (!reuse) { ProfScope ps(prof, cat_fac, 1); factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma); }   // :36
         put_panels(xh, x, n, NP);
+        if (kd) panel_rowscale<T>(st, x, kd, -1, NP, npanel, x);                                    // warm start in the scaled variables: x~ = D^-1 x
         for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
         for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st));     // :39-41
         std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
@@ -1033,7 +1119,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
                 shared_panel<T>(st, SharedPanelOp::product, a_ax);                                  // mA * vX
                 shared_panel<T>(st, SharedPanelOp::product, a_px);                                  // mP * vX
                 shared_panel<T>(st, SharedPanelOp::product, a_aty);                                 // mA' * vY
-                shared_check<T>(st, (int)n, (int)m, NP, MP, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho);   // :64
+                shared_check<T>(st, (int)n, (int)m, NP, MP, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho, kd, ke);   // :64
             }
             HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
             HIPC(hipStreamSynchronize(st));
@@ -1054,7 +1140,8 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         HIPC(hipStreamSynchronize(st));
         prof.harvest();
         const double t2 = now_s();
-        get_panels(x, xh, n, NP);
+        if (kd) { panel_rowscale<T>(st, x, kd, 1, NP, npanel, Px); get_panels(Px, xh, n, NP); }      // x = D x~ (through the check's scratch panel)
+        else get_panels(x, xh, n, NP);
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
             in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
@@ -1091,6 +1178,11 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     // Per-row rho scale (qps_set_shared_rho_scale): rho_i = rho s_i and 1 / rho_i by the caller's row (m long), formed in double and rounded once, for the base
     // rho rs_base (0: stale); the factor object reads them in its numeric factorisation and panel kernels.  They exist only while a scale is set.
     std::vector<double> rho_scale; T *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
+    // Equilibration (qps_set_shared_equilibration): the exponents come from the host copy of the canonical CSC arrays (values rounded to T); while it is on, the
+    // factor's value array and the three CSR value arrays of the check hold the scaled entries, q, l, u hold D q, E l, E u, and kd / ke (n / m ints) are the exponents
+    // on the device.  Ordering, symbolic factor and every index array stay as they are.
+    std::vector<int64_t> hPcp, hPri, hAcp, hAri; std::vector<double> hPnz, hAnz;
+    int *kd = nullptr, *ke = nullptr;
 
     SparseSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, SparseSharedInput&& in, const double* qh, const double* lh, const double* uh) {
         device = dev; n = n_; m = m_; count = cnt;
@@ -1108,6 +1200,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         const int64_t nnzL = (int64_t)in.sym.ci.size(); const int N = in.sym.N, Ns = in.sym.Ns, ldt = in.sym.ldt;
         ldl = make_sparse_ldl<T>(st, std::move(in.sym), in.Pnz.data(), pnnz, in.Anz.data(), annz);
         ldl->panels_prepare(npanel, in.spr);
+        hPcp = std::move(in.Pcp); hPri = std::move(in.Pri); hPnz = std::move(in.Pnz); hAcp = std::move(in.Acp); hAri = std::move(in.Ari); hAnz = std::move(in.Anz);
         const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
         q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
         l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
@@ -1156,15 +1249,92 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     }
     bool update_vectors(const double* qh, const double* lh, const double* uh) override {
         HIPC(hipSetDevice(device));
-        if (qh) put_panels(qh, q, n);
-        if (lh) put_panels(lh, l, m);
-        if (uh) put_panels(uh, u, m);
+        if (qh) { put_panels(qh, q, n); if (kd) panel_rowscale<T>(st, q, kd, 1, (int)n, npanel, q); }          // q~ = D q
+        if (lh) { put_panels(lh, l, m); if (kd) panel_rowscale<T>(st, l, ke, 1, (int)m, npanel, l); }          // l~ = E l, u~ = E u (infinite stays infinite)
+        if (uh) { put_panels(uh, u, m); if (kd) panel_rowscale<T>(st, u, ke, 1, (int)m, npanel, u); }
         return true;   // the factor depends on P, A, rho, sigma only: it stays valid
     }
     void get_dual(double* zh, double* yh) override {
         HIPC(hipSetDevice(device));
-        if (zh) get_panels(z, zh, m);
-        if (yh) get_panels(y, yh, m);
+        if (!kd) {
+            if (zh) get_panels(z, zh, m);
+            if (yh) get_panels(y, yh, m);
+            return;
+        }
+        // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
+        if (zh) { panel_rowscale<T>(st, z, ke, -1, (int)m, npanel, Ax); get_panels(Ax, zh, m); }
+        if (yh) { panel_rowscale<T>(st, y, ke, 1, (int)m, npanel, Ax); get_panels(Ax, yh, m); }
+    }
+    bool takes_equilibration() const override { return true; }
+    // every value array and every vector the handle keeps between calls, in place: *= 2^(+-k) by the host exponents hd / he (device copies in kd / ke)
+    void apply_equilibration(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
+        const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
+        layout::CsrHost Ph = layout::csc_as_transposed_csr(n, n, hPcp, hPri, hPnz), Ah, Ath;
+        layout::csc_to_csr_pair(m, n, hAcp, hAri, hAnz, Ah, Ath);
+        // one exponent per entry, in the order of each value array: the factor's [P; A] in CSC order, then the CSR copies P, A, A'
+        std::vector<int> e((size_t)(2 * pnnz + 3 * annz));
+        int* eK = e.data(); int *eP = eK + pnnz + annz, *eA = eP + pnnz, *eAt = eA + annz;
+        for (int64_t j = 0; j < n; ++j) {
+            for (int64_t k = hPcp[j]; k < hPcp[j + 1]; ++k) eK[k] = hd[hPri[k]] + hd[j];
+            for (int64_t k = hAcp[j]; k < hAcp[j + 1]; ++k) eK[pnnz + k] = he[hAri[k]] + hd[j];
+        }
+        for (int r = 0; r < Ph.nrows; ++r) for (int k = Ph.rp[r]; k < Ph.rp[r + 1]; ++k) eP[k] = hd[r] + hd[Ph.ci[k]];
+        for (int r = 0; r < Ah.nrows; ++r) for (int k = Ah.rp[r]; k < Ah.rp[r + 1]; ++k) eA[k] = he[r] + hd[Ah.ci[k]];
+        for (int r = 0; r < Ath.nrows; ++r) for (int k = Ath.rp[r]; k < Ath.rp[r + 1]; ++k) eAt[k] = hd[r] + he[Ath.ci[k]];
+        int* de = mem.dalloc<int>((int64_t)e.size(), st);
+        if (!e.empty()) up->copy(de, e.data(), sizeof(int) * e.size());
+        ldl->rescale_values(de, sign);
+        scale_entries<T>(st, const_cast<T*>(P.va), de + pnnz + annz, sign, pnnz);
+        scale_entries<T>(st, const_cast<T*>(A.va), de + 2 * pnnz + annz, sign, annz);
+        scale_entries<T>(st, const_cast<T*>(At.va), de + 2 * pnnz + 2 * annz, sign, annz);
+        panel_rowscale<T>(st, q, kd, sign, (int)n, npanel, q);
+        for (T* v : {l, u, z}) panel_rowscale<T>(st, v, ke, sign, (int)m, npanel, v);
+        panel_rowscale<T>(st, y, ke, -sign, (int)m, npanel, y);
+        HIPC(hipStreamSynchronize(st));
+        mem.release(de);
+    }
+    void set_equilibration(int passes) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        // the rule of the dense handle on the host: norms in double from the values rounded to T, read through the exponents
+        std::vector<int> hd, he;
+        if (passes > 0) {
+            const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
+            std::vector<double> aP((size_t)pnnz), aA((size_t)annz), cn((size_t)n), rn((size_t)m);
+            for (int64_t k = 0; k < pnnz; ++k) aP[k] = std::fabs((double)(T)hPnz[k]);
+            for (int64_t k = 0; k < annz; ++k) aA[k] = std::fabs((double)(T)hAnz[k]);
+            hd.assign((size_t)n, 0); he.assign((size_t)m, 0);
+            double hi = 0, lo = INFINITY;
+            for (int pass = 0; pass <= passes; ++pass) {           // the last round only measures the range of the scaled entries
+                std::fill(cn.begin(), cn.end(), 0.0); std::fill(rn.begin(), rn.end(), 0.0);
+                hi = 0; lo = INFINITY;
+                for (int64_t j = 0; j < n; ++j) {
+                    for (int64_t k = hPcp[j]; k < hPcp[j + 1]; ++k) {
+                        const double v = std::ldexp(aP[k], hd[hPri[k]] + hd[j]);
+                        cn[j] = std::fmax(cn[j], v); hi = std::fmax(hi, v); if (v > 0) lo = std::fmin(lo, v);
+                    }
+                    for (int64_t k = hAcp[j]; k < hAcp[j + 1]; ++k) {
+                        const int64_t i = hAri[k];
+                        const double v = std::ldexp(aA[k], he[i] + hd[j]);
+                        cn[j] = std::fmax(cn[j], v); rn[i] = std::fmax(rn[i], v); hi = std::fmax(hi, v); if (v > 0) lo = std::fmin(lo, v);
+                    }
+                }
+                if (pass == passes) break;
+                for (int64_t j = 0; j < n; ++j) hd[j] = std::max(-EQUIL_CLAMP, std::min(EQUIL_CLAMP, hd[j] + equil_step(cn[j])));
+                for (int64_t i = 0; i < m; ++i) he[i] = std::max(-EQUIL_CLAMP, std::min(EQUIL_CLAMP, he[i] + equil_step(rn[i])));
+            }
+            equil_check_range<T>(hi, lo);                          // before anything is modified
+        }
+        if (kd) apply_equilibration(-1, eq_kd, eq_ke);             // the caller's values again, bit for bit
+        mem.release(kd); mem.release(ke); kd = ke = nullptr;
+        eq_kd = hd; eq_ke = he;
+        if (passes > 0) {
+            kd = mem.dalloc<int>(n, st); ke = mem.dalloc<int>(m, st);
+            up->copy(kd, hd.data(), sizeof(int) * (size_t)n);
+            up->copy(ke, he.data(), sizeof(int) * (size_t)m);
+            apply_equilibration(1, hd, he);
+        }
+        factor_valid = false;                                      // the numeric factor belongs to the previous values
     }
     bool takes_rho_scale() const override { return true; }
     bool takes_family_rho() const override { return true; }
@@ -1213,6 +1383,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
             factor_valid = true; fac_rho = rho; fac_sigma = sigma;
         }
         put_panels(xh, x, n);
+        if (kd) panel_rowscale<T>(st, x, kd, -1, (int)n, npanel, x);                                // warm start in the scaled variables: x~ = D^-1 x
         HIPC(hipMemsetAsync(xp, 0, sizeof(T) * (size_t)CP * (size_t)n, st));                        // :38
         for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); // :39-41
         std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
@@ -1255,7 +1426,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
                 csr_panel<T>(st, A, x, (int)n, Ax, (int)m, npanel);                                 // mA * vX
                 csr_panel<T>(st, P, x, (int)n, Px, (int)n, npanel);                                 // mP * vX
                 csr_panel<T>(st, At, y, (int)m, Aty, (int)n, npanel);                               // mA' * vY
-                shared_check<T>(st, (int)n, (int)m, (int)n, (int)m, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho);   // :64
+                shared_check<T>(st, (int)n, (int)m, (int)n, (int)m, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho, kd, ke);   // :64
             }
             HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
             HIPC(hipStreamSynchronize(st));
@@ -1276,7 +1447,8 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         HIPC(hipStreamSynchronize(st));
         prof.harvest();
         const double t2 = now_s();
-        get_panels(x, xh, n);
+        if (kd) { panel_rowscale<T>(st, x, kd, 1, (int)n, npanel, Px); get_panels(Px, xh, n); }      // x = D x~ (through the check's scratch panel)
+        else get_panels(x, xh, n);
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
             in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
@@ -1729,6 +1901,26 @@ QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
     const char* other = "qps_set_shared_adaptive_rho: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) run the family-wide rho rule";
     if (!h->fused_batch || !h->fused_batch->takes_family_rho()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
     h->fused_batch->family_rho = mode;
+    return QPS_OK;
+}
+
+QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (passes < 0 || passes > 50) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_equilibration: passes must be in 0..50 (0 switches the scaling off)");
+    const char* other = "qps_set_shared_equilibration: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) are equilibrated";
+    if (!h->fused_batch || !h->fused_batch->takes_equilibration()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    return guarded(h, [&] { h->fused_batch->set_equilibration(passes); });
+}
+
+QPS_API int32_t qps_get_shared_equilibration(qps_handle hh, double* d_out, double* e_out) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    const char* other = "qps_get_shared_equilibration: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) are equilibrated";
+    if (!h->fused_batch || !h->fused_batch->takes_equilibration()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    const BatchSolverBase& s = *h->fused_batch;
+    for (int64_t j = 0; d_out && j < h->n; ++j) d_out[j] = s.eq_kd.empty() ? 1.0 : std::ldexp(1.0, s.eq_kd[j]);
+    for (int64_t i = 0; e_out && i < h->m; ++i) e_out[i] = s.eq_ke.empty() ? 1.0 : std::ldexp(1.0, s.eq_ke[i]);
     return QPS_OK;
 }
 

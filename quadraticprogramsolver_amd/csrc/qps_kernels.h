@@ -151,7 +151,18 @@ bool shared_panel_small(int rows, int K, size_t elem);   // matrix small enough 
 template <typename T>
 void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* Ax, const T* Px, const T* Aty, const T* q, const T* x, const T* xp,
                   const T* z, const T* zp, unsigned long long* slots, double* res_dev, const int* active, double epsAbs, double epsRel, double epsAdmm,
-                  double rho);
+                  double rho, const int* kd = nullptr, const int* ke = nullptr);
+// kd / ke (both or neither; NP / MP ints): the panels hold iterates scaled by qps_set_shared_equilibration (D = 2^kd on the variables, E = 2^ke on the constraints) and
+// the norms are taken of the unscaled quantities (OSQP 5.1) by a sibling of the norm kernel; without them the launch is the one above, argument for argument.
+// Exact power-of-two Ruiz equilibration of the shared-matrix batches (k_shared.hip).  equil_rownorm: out[r] = 2^kr[r] max_c |M[r][c]| 2^kc[c] in double for a
+// row-major rows x K matrix (ld = K, a multiple of 64); lo != NULL: also the smallest non-zero scaled magnitude per row (+Inf: none).  equil_update: k[i] =
+// clamp(k[i] - floor(e / 2), -13, 13) for max(a[i], b[i]) = f 2^e, f in [0.5, 1) (0: k stays; b may be NULL).  scale_two_sided: M[r][c] *= 2^(sign (kr[r] + kc[c]))
+// in place.  panel_rowscale: dst[panel][row][16] = src 2^(sign k[row]) (dst may be src).  scale_entries: v[i] *= 2^(sign e[i]).
+template <typename T> void equil_rownorm(hipStream_t st, const T* M, int rows, int K, const int* kr, const int* kc, double* out, double* lo);
+void equil_update(hipStream_t st, int len, const double* a, const double* b, int* k);
+template <typename T> void scale_two_sided(hipStream_t st, T* M, int rows, int cols, const int* kr, const int* kc, int sign);
+template <typename T> void panel_rowscale(hipStream_t st, const T* src, const int* k, int sign, int rowsP, int npanel, T* dst);
+template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int sign, int64_t cnt);
 // out[panel][r][16] = sum_k M[r][k] B[panel][k][16] for a plain CSR matrix (k_csr_panel.hip): the check's products of the sparse shared batch.  One 16-lane
 // row per (matrix row, panel), spr strips of it for long rows (csr_panel_spr: from the mean row length), fixed summation order, no atomics.
 // rowsB / rowsOut: rows per panel of B / out.

@@ -43,6 +43,10 @@ template <typename T> struct SparseLdl {
     // the sparse levels and in the dense tail alike -- and iterate_panels() reads them in its right-hand side and row updates; both then ignore the scalar rho.
     // solve(), iterate() and solve_raw() of stand-alone handles do not look at them.
     virtual void set_row_rho(const T* rho_row, const T* rho1_row) = 0;
+    // Equilibration of the shared-matrix batch (qps_set_shared_equilibration): value k of the factor's input array -- [P values; A values] in the caller's CSC
+    // order -- is multiplied by 2^(sign e[k]) in place on the handle's stream (e: device array, one exponent per entry, built by the caller from the pattern).
+    // The pattern, the ordering and the symbolic factor stay; the numeric factor is stale until the next factorize().
+    virtual void rescale_values(const int* e, int sign) = 0;
     virtual const LdlSymbolic& symbolic() const = 0;
     virtual int launches_per_solve() const = 0;
     virtual double bytes_per_solve() const = 0;

@@ -36,6 +36,18 @@ template <typename T> __device__ __forceinline__ T wave_sum_all(T a) {
     t = t + dpp_get<0x143, 0xc, 0xf>(t);            // row_bcast:31 into rows 2 and 3: lane 63 holds the wave sum
     return lane_get(t, 63);
 }
+// maximum over the 64 lanes of the wave of values that are >= 0 (a lane without a DPP source contributes 0), returned in every lane: the steps of
+// wave_sum_all with max in place of +
+template <typename T> __device__ __forceinline__ T wave_max_all_nonneg(T a) {
+    T t = fmax(a, dpp_get<0x111, 0xf, 0xf>(a));
+    t = fmax(t, dpp_get<0x112, 0xf, 0xf>(a));
+    t = fmax(t, dpp_get<0x113, 0xf, 0xf>(a));
+    t = fmax(t, dpp_get<0x114, 0xf, 0xe>(t));
+    t = fmax(t, dpp_get<0x118, 0xf, 0xc>(t));
+    t = fmax(t, dpp_get<0x142, 0xa, 0xf>(t));
+    t = fmax(t, dpp_get<0x143, 0xc, 0xf>(t));
+    return lane_get(t, 63);
+}
 // sum of lanes 0..7 (other lanes ignored), returned in every lane
 template <typename T> __device__ __forceinline__ T lanes8_sum_all(T a) {
     T t = a + dpp_get<0x111, 0xf, 0xf>(a);

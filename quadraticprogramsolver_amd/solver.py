@@ -346,6 +346,19 @@ class QuadraticProgramSharedBatch(_Handle):
         stays refused."""
         _lib.check(_lib.lib().qps_set_shared_adaptive_rho(self._h, 1 if on else 0), self._h)
 
+    def set_equilibration(self, passes=10):
+        """Ruiz equilibration with exact powers of two (qps_set_shared_equilibration; OSQP §5.1), opt-in: ``passes`` = 1..50 passes of the rule, computed once for the
+        family from mP and mA; ``0`` or ``None`` switches it off and restores the matrices bit for bit.  The loop runs on D P D, E A D, D q, E l, E u; warm starts,
+        results, ``dual()`` and the convergence check stay in the caller's units.  Setting, changing or clearing makes the next ``solve`` factorise, also with
+        ``reuseFactor=True``.  QPS_ERR_UNSUPPORTED when a scaled matrix entry would leave the normal range of the handle's type (the handle stays as it was)."""
+        _lib.check(_lib.lib().qps_set_shared_equilibration(self._h, 0 if passes is None else int(passes)), self._h)
+
+    def equilibration(self):
+        """(vD [n], vE [m]) of ``set_equilibration``: powers of two, all ones while it is off (qps_get_shared_equilibration)."""
+        vD, vE = np.zeros(self.n), np.zeros(self.m)
+        _lib.check(_lib.lib().qps_get_shared_equilibration(self._h, _dp(vD), _dp(vE)), self._h)
+        return vD, vE
+
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
         """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts), as ``QuadraticProgramBatch.solve``.  ``mX`` (optional) holds the warm starts."""
