@@ -37,8 +37,8 @@ P x = d o x + U (U'x).  ``admm_loop`` restates SolveQuadraticProgram.jl:45-71 wi
 Cases ("entry": the first n of a band, ragged inside its 64-pad -- a dispatch off-by-one, the mask of a barely used chunk; "last": 4 real columns
 in the last chunk the instantiation has -- chunk addressing with every chunk live).  NP, B, the instantiations: ``CASES`` / ``PQ_CASES`` below.
 Not covered: fp32 beyond n = 24576 (sweep KC 16 in fp32; its host matrix alone is 4.9 GB, and the fp64 KC 16 cases run the same template code);
-the polishing pass (MODE 2, apass_kkt: the same bands, but it needs a converged state and a MINRES restatement at these sizes); batched passes
-beyond KC 2; the blocked sweeps (variants 1 and 5).
+batched passes beyond KC 2; the blocked sweeps (variants 1 and 5).  The polishing pass (MODE 2, apass_kkt: the same bands) has its own table,
+tests/polish_band_cases.py: it needs neither a converged state nor MINRES iteration counts, because its active sets are the signs of a chosen y.
 
 Bounds.  fp64: TOL["f64"] of loop_param_cases.py (ProxQP: the bounds of test_iterates_and_report_match_oracle).  fp32: 100 x the error of the
 fp32 emulation against the fp64 reference, recorded once per case in EMU_F32 (the CPU guards repeat the emulation for n <= 4100 only; the larger
