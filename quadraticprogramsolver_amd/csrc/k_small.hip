@@ -480,8 +480,9 @@ void admm_small(hipStream_t st, int n, int m, int NP, int MP, int it_begin, int 
                 const T* At, const T* P, const T* S, const T* q, const T* l, const T* u, T* x, T* xp, T* z, T* y, void* out_dev) {
     SmallArgs a{n, m, NP, MP, it_begin, it_end, numItrConv, adptRho, rho, rhorho, sigma, alpha, epsAbs, epsRel, epsAdmm, fctrRho};
     static const int reg_env = [] { const char* e = getenv("QPS_SMALL_REG"); return e ? atoi(e) : 1; }();
-    // matrices in registers: n <= 64 with m <= 128 (fp64) / 256 (fp32); n <= 128 with m <= 64 (fp64) / 128 (fp32) -- beyond that the
-    // per-thread share of A (twice) and S no longer fits the 256 VGPRs of an 8-wave workgroup without spilling
+    // matrices in registers: NP = 64 or 128 with MP / 64 <= 2 (fp64: m <= 128) / 4 (fp32: m <= 256), the same row limit at both widths --
+    // beyond that the per-thread share of A (twice) and S no longer fits the 256 VGPRs of an 8-wave workgroup (fp64 <2, 2> sits at that
+    // limit and already spills: DESIGN section 9)
     if (reg_env && MP >= 64 && (NP == 64 || NP == 128)) {
         SmallOut* o = reinterpret_cast<SmallOut*>(out_dev);
         const int mb = MP / 64, mb_max = sizeof(T) == 8 ? 2 : 4;
