@@ -287,6 +287,27 @@ int32_t qps_set_shared_adaptive_rho(qps_handle h, int32_t mode /* 0 fixed rho, 1
 int32_t qps_set_shared_equilibration(qps_handle h, int32_t passes /* 0 = off (default); 1..50 = that many Ruiz passes */);
 int32_t qps_get_shared_equilibration(qps_handle h, double *d_out /* [n] or NULL */, double *e_out /* [m] or NULL */);
 
+/* Warm start of z and y across the re-solves of a shared-matrix batch handle (dense or sparse; the OSQP paper warm-starts (x, y) and continues from (x, z, y)),
+ * opt-in.  The handle keeps z and y of every column between calls; both are zero from creation on.  mode is a property of the handle and persists across solves:
+ *   0 (the default): qps_solve_batch restarts z and y at 0 (SolveQuadraticProgram.jl:39-40); x alone comes from x_inout.
+ *   1 ("state"): every column starts from the z and y the handle holds -- the iterates at the column's own stopping iteration of the last qps_solve_batch, or what
+ *      qps_set_shared_dual wrote since -- and from the x of x_inout.  On a fresh handle this is the cold start, bit for bit.
+ *   2 ("Ax", OSQP's warm_start(x, y)): y comes from the handle and z = A x is formed on the device from the x_inout of this solve, without projection.
+ * In modes 1 and 2 xp and zp start at 0 (iteration 1 overwrites them before a check reads them), the iteration counter restarts at 1 -- checks fall on multiples
+ * of numItrConv of this solve -- and flags, iterations, residuals, reuseFactor, the family-wide rho rule and qps_info keep their meaning.  A stored z outside new
+ * bounds is legal: iteration 1 clamps it.  z and y do not depend on rho: setting or clearing a rho scale or changing qps_params.rho leaves them alone (the dense
+ * handle re-forms rho_i z - y for the rho of the solve in one launch), and a change of the equilibration carries them over in the caller's units.  Together with
+ * qps_update_shared_vectors and reuseFactor = 1 a re-solve then neither factorises nor starts its iterations over.
+ * qps_set_shared_dual is the counterpart of qps_get_dual: z and / or y, [count][m] each in the caller's units (with equilibration on the handle stores E z and
+ * E^-1 y: exact powers of two, so writing back what qps_get_dual returned changes no bit, for fp64 and fp32 handles alike).  The arrays are copied; a NULL
+ * pointer keeps that array.
+ * After a qps_solve_batch that returned an error the stored z and y are unspecified until qps_set_shared_dual or a mode-0 solve.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, a mode outside 0..2 (judged before the kind of handle), or a NaN / Inf entry of z or y (before a device is needed; the
+ * handle keeps its state).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch.
+ * Out of scope: stand-alone handles, qps_create_dense_batch, ProxQP handles (qps_proxqp_set_state serves them) and polishing. */
+int32_t qps_set_shared_warm_start(qps_handle h, int32_t mode /* 0 z = y = 0 (default), 1 the stored z and y, 2 z = A x and the stored y */);
+int32_t qps_set_shared_dual(qps_handle h, const double *z, const double *y);   /* [count][m] each; NULL keeps that array */
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads

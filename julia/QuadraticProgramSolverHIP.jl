@@ -431,6 +431,27 @@ function SharedBatchEquilibration(sb::SharedBatchHip)
     return vD, vE
 end
 
+# Warm start of z and y across re-solves (qps_set_shared_warm_start), opt-in: mode 0 / nothing / false / :off restarts z = y = 0 (the default), 1 / true / :state
+# starts every column from the z and y the handle holds (the last SharedBatchSolve!, or SharedBatchSetDual! since), 2 / :ax takes y from the handle and forms
+# z = A x on the device from the mX of the solve (OSQP's warm_start(x, y)).  The setting stays with the handle.
+function SharedBatchSetWarmStart!(sb::SharedBatchHip, mode::Union{Nothing, Bool, Integer, Symbol} = :state)
+    h = sb.h
+    md = mode === nothing || mode === false || mode === :off ? 0 : (mode === true || mode === :state ? 1 : (mode === :ax ? 2 : mode))
+    md isa Integer || throw(ArgumentError("mode must be nothing, a Bool, 0..2, :off, :state or :ax"))
+    _check(ccall((:qps_set_shared_warm_start, LIBQPS), Int32, (Ptr{Cvoid}, Int32), h, md), h)
+    return nothing
+end
+
+# z and / or y of every column (m x count each, the caller's units; qps_set_shared_dual, the counterpart of qps_get_dual).  nothing keeps that array.
+function SharedBatchSetDual!(sb::SharedBatchHip; mZ::Union{Nothing, Matrix{Float64}} = nothing, mY::Union{Nothing, Matrix{Float64}} = nothing)
+    h = sb.h
+    (mZ === nothing || size(mZ) == (sb.m, sb.count)) || throw(DimensionMismatch("mZ must be m x count"))
+    (mY === nothing || size(mY) == (sb.m, sb.count)) || throw(DimensionMismatch("mY must be m x count"))
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve mZ mY _check(ccall((:qps_set_shared_dual, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h, p(mZ), p(mY)), h)
+    return nothing
+end
+
 # factor on the rows that are equalities (l == u) in every column of mL / mU (m x count), 1 elsewhere
 EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
 

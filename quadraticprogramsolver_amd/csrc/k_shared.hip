@@ -52,6 +52,10 @@ template <> struct PanelMfma<float> {
 __device__ __forceinline__ unsigned long long sh_absbits(double v) { return (unsigned long long)__double_as_longlong(fabs(v)); }
 __device__ __forceinline__ unsigned long long sh_umax(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
+// w = rho_i z - y, the operand of the next right-hand side (LinearSystemSolvers.jl:134-135): ONE expression for the row epilogues of k_panel and for k_panel_w,
+// so that a w re-formed from a stored (z, y) carries the bits the row update would have left behind
+template <typename T> __device__ __forceinline__ T panel_w_of(T rr, T z, T y) { return rr * z - y; }
+
 // waves per workgroup (k split): 8, or 16 for matrices small enough to sit in the caches (shared_panel_small)
 constexpr int SH_KS = 32;     // matrix columns per step
 
@@ -127,6 +131,8 @@ struct PanelStep {
 // EPI: 0 out = s;  1 out = sigma x - q + s (right-hand side, LinearSystemSolvers.jl:136);  2 s = x~: out = s, xp = x, x = alpha s + (1 - alpha) x
 // (SolveQuadraticProgram.jl:56-57);  3 s = z~: zp = z, z = clamp(...), y += rho (...), w = rho z - y (:59-61 and the next :134-135);
 // 4 = 3 with rho read as diag(rho_i): rho_i and 1 / rho_i of the output row come from a.rho_row / a.rho1_row (two cached loads per output element)
+// 5 s = A x~ of a warm start (qps_set_shared_warm_start, mode 2): z = s without projection, w = rho_i z - y with the stored y; rho_i = a.rho_row[row], or a.rho
+// when a.rho_row is NULL
 template <typename T, int TRI, int EPI, int PB, int SH_NW, bool STG>
 __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
     using S = PanelStep<T, TRI, PB, STG>;
@@ -207,9 +213,9 @@ __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
                 const T zn = t > hi ? hi : (t < lo ? lo : t);
                 const T yn = yo + a.rho * (a.alpha * sum + alpha1 * zo - zn);   // :61
                 a.z[idx] = zn; a.y[idx] = yn;
-                a.w[idx] = a.rho * zn - yn;                              // LinearSystemSolvers.jl:134-135 of the next iteration
+                a.w[idx] = panel_w_of(a.rho, zn, yn);                        // LinearSystemSolvers.jl:134-135 of the next iteration
             }
-        } else {
+        } else if (EPI == 4) {
             if (a.active[P * 16 + col]) {
                 const T rr = a.rho_row[r0 + row], rr1 = a.rho1_row[r0 + row];   // rho_i, 1 / rho_i: r0 + row < a.rows, the vectors' length
                 const T zo = a.z[idx], yo = a.y[idx];
@@ -219,7 +225,13 @@ __global__ __launch_bounds__(SH_NW * 64) void k_panel(PanelArgs<T> a) {
                 const T zn = t > hi ? hi : (t < lo ? lo : t);
                 const T yn = yo + rr * (a.alpha * sum + alpha1 * zo - zn);      // :61
                 a.z[idx] = zn; a.y[idx] = yn;
-                a.w[idx] = rr * zn - yn;                                 // LinearSystemSolvers.jl:134-135 of the next iteration
+                a.w[idx] = panel_w_of(rr, zn, yn);                           // LinearSystemSolvers.jl:134-135 of the next iteration
+            }
+        } else {
+            if (a.active[P * 16 + col]) {
+                const T rr = a.rho_row ? a.rho_row[r0 + row] : a.rho;        // r0 + row < a.rows, the vector's length
+                a.z[idx] = sum;
+                a.w[idx] = panel_w_of(rr, sum, a.y[idx]);                    // LinearSystemSolvers.jl:134-135 of the first iteration
             }
         }
     }
@@ -444,7 +456,7 @@ __global__ __launch_bounds__(256) void k_panel_w(const T* __restrict__ z, const 
 #pragma unroll
     for (int j = 0; j < VN; ++j) {
         const T zn = zv[j], yn = yv[j];
-        if (active[P * 16 + col + j]) wv[j] = rr * zn - yn;
+        if (active[P * 16 + col + j]) wv[j] = panel_w_of(rr, zn, yn);
     }
     reinterpret_cast<NV*>(w)[i] = wv;
 }
@@ -483,6 +495,7 @@ void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a) {
         case SharedPanelOp::backward_x: panel_shape<T, 2, 2>(st, a); break;
         case SharedPanelOp::rows_zy: panel_shape<T, 0, 3>(st, a); break;
         case SharedPanelOp::rows_zy_scaled: panel_shape<T, 0, 4>(st, a); break;
+        case SharedPanelOp::start_z: panel_shape<T, 0, 5>(st, a); break;
     }
 }
 

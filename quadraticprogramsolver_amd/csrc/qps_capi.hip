@@ -558,6 +558,9 @@ struct BatchSolverBase {
     virtual bool takes_equilibration() const { return false; }                        // shared-matrix batches only
     virtual void set_equilibration(int passes) { (void)passes; }                      // passes: 0..50 validated by the caller
     std::vector<int> eq_kd, eq_ke;                                                    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
+    virtual bool takes_warm_start() const { return false; }                           // shared-matrix batches only: z and y stay on the handle between solves
+    int warm_start = 0;                                                               // qps_set_shared_warm_start: 0 z = y = 0, 1 the stored (z, y), 2 z = A x and the stored y
+    virtual void set_dual(const double* z, const double* y) { (void)z; (void)y; }     // [count][m] each, finite (validated by the caller); NULL keeps that array
 };
 
 // Ruiz equilibration of the shared-matrix batches with exact powers of two (qps_set_shared_equilibration).  The step for a norm v = f 2^e, f in [0.5, 1), is
@@ -869,7 +872,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
     int* fail = nullptr; int* d_active = nullptr; int* h_int = nullptr;
     unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
     bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0, cat_fac = 0, cat_switch = 0;
+    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0, cat_fac = 0, cat_switch = 0, cat_start = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
     // Per-row rho scale (qps_set_shared_rho_scale): row i runs with rho_i = rho s_i.  Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so
     // M = PI + rho Ws'Ws comes out of the same symmetric product and a change of the base rho alone only re-assembles; rs_rho / rs_rho1 hold rho_i and 1 / rho_i
@@ -892,6 +895,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         yv = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
         l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st);
         w = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
+        for (T* v : {z, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)pm, st));                 // the state qps_set_shared_warm_start continues from is defined from creation on
         fail = mem.dalloc<int>(4, st); d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
         slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
         stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
@@ -904,6 +908,7 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         cat_chk = prof.category("shared: check (A x, P x, A'y, norms)", s * (2.0 * m * n + (double)n * n + c * (8.0 * n + 6.0 * m)));
         cat_fac = prof.category("shared: factorisation at setup", s * ((double)m * n + 4.0 * n * n));
         cat_switch = prof.category("shared: rho switch (assemble, Cholesky, w)", s * (3.0 * n * n + 3.0 * c * m));
+        cat_start = prof.category("shared: warm start (w, or A x -> z, w)", s * 3.0 * c * m);
     }
     ~SharedBatchSolver() override {
         (void)hipSetDevice(device);
@@ -946,6 +951,13 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
         if (zh) { panel_rowscale<T>(st, z, ke, -1, MP, npanel, Ax); get_panels(Ax, zh, m, MP); }
         if (yh) { panel_rowscale<T>(st, y, ke, 1, MP, npanel, Ax); get_panels(Ax, yh, m, MP); }
+    }
+    bool takes_warm_start() const override { return true; }
+    void set_dual(const double* zh, const double* yh) override {   // the counterpart of get_dual: z~ = E z, y~ = E^-1 y
+        HIPC(hipSetDevice(device));
+        if (zh) { put_panels(zh, z, m, MP); if (kd) panel_rowscale<T>(st, z, ke, 1, MP, npanel, z); }
+        if (yh) { put_panels(yh, y, m, MP); if (kd) panel_rowscale<T>(st, y, ke, -1, MP, npanel, y); }
+        HIPC(hipStreamSynchronize(st));
     }
     bool takes_equilibration() const override { return true; }
     // the matrices and every vector the handle keeps between calls, in place: *= 2^(+-k) by the exponents in kd / ke
@@ -1071,7 +1083,9 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
         put_panels(xh, x, n, NP);
         if (kd) panel_rowscale<T>(st, x, kd, -1, NP, npanel, x);                                    // warm start in the scaled variables: x~ = D^-1 x
         for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
-        for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st));     // :39-41
+        const int warm = warm_start;
+        if (warm == 0) { for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st)); }   // :39-41
+        else { for (T* v : {zp, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st)); }  // z (mode 1) and y stay: iteration 1 overwrites zp before a check reads it
         std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
         std::vector<double> resP(count, NAN), resD(count, NAN);
         for (int b = 0; b < count; ++b) active[b] = 1;
@@ -1081,6 +1095,15 @@ template <typename T> struct SharedBatchSolver : BatchSolverBase {
             HIPC(hipStreamSynchronize(st));   // the pinned staging is reused
         };
         push_active();
+        if (warm == 1) {                                                                            // w = rho_i z - y for this solve's rho: what the row update would have left
+            ProfScope ps(prof, cat_start, 1);
+            panel_w<T>(st, z, y, d_active, scaled ? rs_rho : nullptr, (T)rho, MP, npanel, w);
+        } else if (warm == 2) {                                                                     // OSQP's warm_start(x, y): z = A x~ without projection, w with the stored y
+            ProfScope ps(prof, cat_start, 1);
+            PanelArgs<T> a_st = product_args(A, NP, MP, NP, x, nullptr);
+            a_st.z = z; a_st.y = y; a_st.w = w; a_st.rho = (T)rho; a_st.rho_row = scaled ? rs_rho : nullptr;
+            shared_panel<T>(st, SharedPanelOp::start_z, a_st);
+        }
         const double t1 = now_s();
         PanelArgs<T> a_rhs = product_args(At, MP, NP, MP, w, tt); a_rhs.x = x; a_rhs.q = q; a_rhs.sigma = (T)sigma;
         PanelArgs<T> a_fwd = product_args(S, NP, NP, NP, tt, yv);
@@ -1173,7 +1196,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
     int* d_active = nullptr; int* h_int = nullptr;
     unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
     bool factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    LdlPanelProf pf; int cat_chk = 0, cat_fac = 0, cat_switch = 0;
+    LdlPanelProf pf; int cat_chk = 0, cat_fac = 0, cat_switch = 0, cat_start = 0;
     std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
     // Per-row rho scale (qps_set_shared_rho_scale): rho_i = rho s_i and 1 / rho_i by the caller's row (m long), formed in double and rounded once, for the base
     // rho rs_base (0: stale); the factor object reads them in its numeric factorisation and panel kernels.  They exist only while a scale is set.
@@ -1204,6 +1227,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
         q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
         l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
+        for (T* v : {z, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)pm, st));                 // the state qps_set_shared_warm_start continues from is defined from creation on
         d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
         slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
         stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
@@ -1219,6 +1243,7 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         cat_chk = prof.category("sparse shared: check (A x, P x, A'y, norms)", np * (2.0 * annz + pnnz) * (s + 4) + s * c * ((2.0 * annz + pnnz) + 8.0 * n + 6.0 * m));
         cat_fac = prof.category("sparse shared: factorisation at setup", (s + 4) * ents + s * (pnnz + annz));
         cat_switch = prof.category("sparse shared: rho switch (numeric L D L')", (s + 4) * ents + s * (pnnz + annz));
+        cat_start = prof.category("sparse shared: warm start (A x -> z)", np * annz * (s + 4) + s * c * (annz + m));
         update_vectors(qh, lh, uh);
     }
     ~SparseSharedBatchSolver() override {
@@ -1264,6 +1289,13 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
         if (zh) { panel_rowscale<T>(st, z, ke, -1, (int)m, npanel, Ax); get_panels(Ax, zh, m); }
         if (yh) { panel_rowscale<T>(st, y, ke, 1, (int)m, npanel, Ax); get_panels(Ax, yh, m); }
+    }
+    bool takes_warm_start() const override { return true; }
+    void set_dual(const double* zh, const double* yh) override {   // the counterpart of get_dual: z~ = E z, y~ = E^-1 y
+        HIPC(hipSetDevice(device));
+        if (zh) { put_panels(zh, z, m); if (kd) panel_rowscale<T>(st, z, ke, 1, (int)m, npanel, z); }
+        if (yh) { put_panels(yh, y, m); if (kd) panel_rowscale<T>(st, y, ke, -1, (int)m, npanel, y); }
+        HIPC(hipStreamSynchronize(st));
     }
     bool takes_equilibration() const override { return true; }
     // every value array and every vector the handle keeps between calls, in place: *= 2^(+-k) by the host exponents hd / he (device copies in kd / ke)
@@ -1385,7 +1417,10 @@ template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
         put_panels(xh, x, n);
         if (kd) panel_rowscale<T>(st, x, kd, -1, (int)n, npanel, x);                                // warm start in the scaled variables: x~ = D^-1 x
         HIPC(hipMemsetAsync(xp, 0, sizeof(T) * (size_t)CP * (size_t)n, st));                        // :38
-        for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); // :39-41
+        const int warm = warm_start;
+        if (warm == 0) { for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); }   // :39-41
+        else HIPC(hipMemsetAsync(zp, 0, sizeof(T) * (size_t)CP * (size_t)m, st));                   // z (mode 1) and y stay; the first right-hand side is built from them (rhs_ready)
+        if (warm == 2) { ProfScope ps(prof, cat_start, 1); csr_panel<T>(st, A, x, (int)n, z, (int)m, npanel); }   // OSQP's warm_start(x, y): z = A x~ without projection
         std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
         std::vector<double> resP(count, NAN), resD(count, NAN);
         for (int b = 0; b < count; ++b) active[b] = 1;
@@ -1902,6 +1937,27 @@ QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
     if (!h->fused_batch || !h->fused_batch->takes_family_rho()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
     h->fused_batch->family_rho = mode;
     return QPS_OK;
+}
+
+QPS_API int32_t qps_set_shared_warm_start(qps_handle hh, int32_t mode) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (mode < 0 || mode > 2) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_warm_start: mode must be 0 (z = y = 0), 1 (the stored z and y) or 2 (z = A x, the stored y)");
+    const char* other = "qps_set_shared_warm_start: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) keep z and y between solves";
+    if (!h->fused_batch || !h->fused_batch->takes_warm_start()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    h->fused_batch->warm_start = mode;
+    return QPS_OK;
+}
+
+QPS_API int32_t qps_set_shared_dual(qps_handle hh, const double* z, const double* y) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    const char* other = "qps_set_shared_dual: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) keep z and y between solves";
+    if (!h->fused_batch || !h->fused_batch->takes_warm_start()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    const int64_t c = h->fused_batch->count;
+    if (z && !all_finite(z, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_dual: z contains NaN/Inf (the handle keeps its state)");
+    if (y && !all_finite(y, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_dual: y contains NaN/Inf (the handle keeps its state)");
+    return guarded(h, [&] { h->fused_batch->set_dual(z, y); });
 }
 
 QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {

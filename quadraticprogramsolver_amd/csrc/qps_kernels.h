@@ -142,7 +142,8 @@ enum class SharedPanelOp {
     backward,     // out = triu(Mat) B                                               backward sweep alone (dense tail of the sparse shared batch)
     backward_x,   // out = triu(Mat) B; active columns: xp = x, x = alpha out + (1 - alpha) x      backward sweep + SolveQuadraticProgram.jl:56-57
     rows_zy,      // s = Mat B = z~; active columns: zp = z, z, y updated, w = rho z - y           SolveQuadraticProgram.jl:59-61
-    rows_zy_scaled   // rows_zy with rho read as diag(rho_i): row r takes rho_row[r] and rho1_row[r] in z, y and w (qps_set_shared_rho_scale)
+    rows_zy_scaled,  // rows_zy with rho read as diag(rho_i): row r takes rho_row[r] and rho1_row[r] in z, y and w (qps_set_shared_rho_scale)
+    start_z          // s = Mat B = A x~; active columns: z = s, w = rho_i z - y (rho_i = rho_row[r], or rho when rho_row is NULL)     qps_set_shared_warm_start, mode 2
 };
 template <typename T> void shared_panel(hipStream_t st, SharedPanelOp op, const PanelArgs<T>& a);
 bool shared_panel_small(int rows, int K, size_t elem);   // matrix small enough to stay cached: one panel and 16 waves per workgroup

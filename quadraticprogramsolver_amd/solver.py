@@ -359,6 +359,26 @@ class QuadraticProgramSharedBatch(_Handle):
         _lib.check(_lib.lib().qps_get_shared_equilibration(self._h, _dp(vD), _dp(vE)), self._h)
         return vD, vE
 
+    _WARM_MODES = {None: 0, False: 0, "off": 0, True: 1, "state": 1, "ax": 2}
+
+    def set_warm_start(self, mode="state"):
+        """Warm start of z and y across re-solves (qps_set_shared_warm_start), opt-in.  ``None`` / ``False`` / ``"off"``: every ``solve`` restarts z = y = 0 (the
+        default).  ``True`` / ``"state"``: every column starts from the z and y the handle holds -- those of its own stopping iteration of the last ``solve``, or
+        what ``set_dual`` wrote since -- and from ``mX``.  ``"ax"``: OSQP's warm_start(x, y); y from the handle, z = A x formed on the device from ``mX``.  The
+        setting stays with the handle; with ``update`` and ``solve(reuseFactor=True)`` a re-solve neither factorises nor starts its iterations over."""
+        if isinstance(mode, (bool, str, type(None))):
+            if mode not in self._WARM_MODES:
+                raise ValueError(f"mode must be one of None, False, 'off', True, 'state', 'ax' (got {mode!r})")
+            mode = self._WARM_MODES[mode]
+        _lib.check(_lib.lib().qps_set_shared_warm_start(self._h, int(mode)), self._h)
+
+    def set_dual(self, mZ=None, mY=None):
+        """Writes z and / or y of every column ([count x m], the caller's units; qps_set_shared_dual, the counterpart of ``dual``).  ``None`` keeps that array."""
+        z = None if mZ is None else self._rows(mZ, "mZ", self.m)
+        y = None if mY is None else self._rows(mY, "mY", self.m)
+        ptr = lambda a: None if a is None else _dp(a)
+        _lib.check(_lib.lib().qps_set_shared_dual(self._h, ptr(z), ptr(y)), self._h)
+
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
         """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts), as ``QuadraticProgramBatch.solve``.  ``mX`` (optional) holds the warm starts."""
