@@ -1,0 +1,57 @@
+// qps_batch.h -- what the batch handles share between qps_capi.hip (handle plumbing, BatchedDenseSolver) and qps_shared_batch.hip (the shared-matrix family):
+// the base of every fused batch solver, the one interface the qps_*_shared_* entry points talk to, the factories of the family, and the panelled matrix upload.
+#pragma once
+#include "ldl_symbolic.h"
+#include "qps_internal.h"
+#include "qps_kernels.h"
+
+namespace qps {
+
+// What only the shared-matrix batches take (qps_update_shared_vectors, qps_set_shared_*, qps_get_shared_equilibration); arrays validated by the caller.
+struct SharedFamilyOps {
+    int family_rho = 0;               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule (one factor, hence one rho to move)
+    int warm_start = 0;               // qps_set_shared_warm_start: 0 z = y = 0, 1 the stored (z, y), 2 z = A x and the stored y
+    std::vector<int> eq_kd, eq_ke;    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
+    virtual ~SharedFamilyOps() {}
+    virtual void update_vectors(const double* q, const double* l, const double* u) = 0;   // [count][n], [count][m], [count][m]; NULL keeps that array
+    virtual void set_rho_scale(const double* scale) = 0;                                  // [m], or NULL
+    virtual void set_equilibration(int passes) = 0;                                       // 0..50
+    virtual void set_dual(const double* z, const double* y) = 0;                          // [count][m] each, finite; NULL keeps that array
+};
+
+struct BatchSolverBase {
+    int device = 0; int64_t n = 0, m = 0; int count = 0; std::string err; Profiler prof;
+    virtual ~BatchSolverBase() {}
+    virtual void solve_batch(double* x, const qps_params& p, qps_info* infos) = 0;
+    virtual void get_dual(double* z, double* y) = 0;   // [count][m] each
+    virtual SharedFamilyOps* shared_family() { return nullptr; }   // the shared-matrix batches only
+};
+
+struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
+    LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;
+};
+int shared_batch_max_np(int dtype);   // the largest padded n of a dense shared-matrix batch
+BatchSolverBase* make_dense_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda,
+                                         const double* q, const double* l, const double* u);
+BatchSolverBase* make_sparse_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, SparseSharedInput&& in, const double* q, const double* l,
+                                          const double* u);
+
+// column-major host matrix (rows x cols, ld ldh) -> row-major device T (ld ldd), streamed through a bounded device staging buffer in column panels
+template <typename T>
+inline void upload_matrix_panels(hipStream_t st, int device, const double* h, int64_t ldh, int rows, int cols, T* d, int64_t ldd) {
+    if (rows <= 0 || cols <= 0) return;
+    const int64_t budget = (int64_t)32 << 20;   // doubles per panel (256 MiB)
+    int pc = (int)std::max<int64_t>(64, (budget / std::max(rows, 1)) / 64 * 64);
+    DeviceOwner tmp_mem;
+    double* buf = tmp_mem.alloc<double>((int64_t)rows * std::min(pc, cols));
+    FastUploader fu(st, device);                 // pinned ring filled by several host threads (qps_internal.h)
+    for (int c0 = 0; c0 < cols; c0 += pc) {
+        const int nc = std::min(pc, cols - c0);
+        if (ldh == rows) fu.copy(buf, h + (int64_t)c0 * ldh, sizeof(double) * (size_t)rows * (size_t)nc);
+        else for (int c = 0; c < nc; ++c) fu.copy(buf + (int64_t)c * rows, h + (int64_t)(c0 + c) * ldh, sizeof(double) * (size_t)rows);
+        import_colmajor<T>(st, buf, rows, rows, nc, d + c0, ldd);
+        HIPC(hipStreamSynchronize(st));
+    }
+}
+
+}  // namespace qps

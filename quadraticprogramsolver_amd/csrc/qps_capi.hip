@@ -1,4 +1,6 @@
-// qps_capi.hip -- the C ABI of include/qps.h: handle table, problem import, the device-resident ADMM loop driver.
+// qps_capi.hip -- the C ABI of include/qps.h: per-device resource pools, handle table, argument validation and problem import of every entry point, and the
+// device-resident ADMM loop drivers of the dense handles (DenseSolver, BatchedDenseSolver).  The shared-matrix batches live in qps_shared_batch.hip, the sparse
+// handles in k_sparse.hip, ProxQP in qps_proxqp.hip; this file builds them through the factories of qps_batch.h / qps_internal.h / qps_proxqp.h.
 //
 // Loop structure follows SolveQuadraticProgram.jl:36-73; the linear solve is the reduced form of
 // LinearSystemSolvers.jl:110-142 with cg! replaced by Cholesky + two triangular sweeps (ProxQP.jl:175-206,221-225).
@@ -11,6 +13,7 @@
 
 #include "batch_schedule.h"
 #include "dense_chol.h"
+#include "qps_batch.h"
 #include "qps_internal.h"
 #include "spmv_layout.h"
 #include "qps_kernels.h"
@@ -105,24 +108,6 @@ ProfLaunchScope::~ProfLaunchScope() {
 namespace {
 
 thread_local std::string g_last_error;
-
-// column-major host matrix (rows x cols, ld ldh) -> row-major device T (ld ldd), streamed through a bounded device staging buffer in column panels
-template <typename T>
-void upload_matrix_panels(hipStream_t st, int device, const double* h, int64_t ldh, int rows, int cols, T* d, int64_t ldd) {
-    if (rows <= 0 || cols <= 0) return;
-    const int64_t budget = (int64_t)32 << 20;   // doubles per panel (256 MiB)
-    int pc = (int)std::max<int64_t>(64, (budget / std::max(rows, 1)) / 64 * 64);
-    DeviceOwner tmp_mem;
-    double* buf = tmp_mem.alloc<double>((int64_t)rows * std::min(pc, cols));
-    FastUploader fu(st, device);                 // pinned ring filled by several host threads (qps_internal.h)
-    for (int c0 = 0; c0 < cols; c0 += pc) {
-        const int nc = std::min(pc, cols - c0);
-        if (ldh == rows) fu.copy(buf, h + (int64_t)c0 * ldh, sizeof(double) * (size_t)rows * (size_t)nc);
-        else for (int c = 0; c < nc; ++c) fu.copy(buf + (int64_t)c * rows, h + (int64_t)(c0 + c) * ldh, sizeof(double) * (size_t)rows);
-        import_colmajor<T>(st, buf, rows, rows, nc, d + c0, ldd);
-        HIPC(hipStreamSynchronize(st));
-    }
-}
 
 // =================================================================================================================
 // Dense problem, Cholesky path
@@ -545,63 +530,6 @@ template <typename T> struct DenseSolver : SolverBase {
 // (blockIdx.y = QP); rho, the proposed rho, the convergence flag and the active mask are per QP, exactly as if each QP
 // ran its own SolveQuadraticProgram! (the tests compare every QP of a batch with its own stand-alone run).
 // =================================================================================================================
-struct BatchSolverBase {
-    int device = 0; int64_t n = 0, m = 0; int count = 0; std::string err; Profiler prof;
-    virtual ~BatchSolverBase() {}
-    virtual void solve_batch(double* x, const qps_params& p, qps_info* infos) = 0;
-    virtual void get_dual(double* z, double* y) = 0;   // [count][m] each
-    virtual bool update_vectors(const double* q, const double* l, const double* u) { (void)q; (void)l; (void)u; return false; }   // shared-matrix batches only
-    virtual bool takes_rho_scale() const { return false; }                            // shared-matrix batches only
-    virtual void set_rho_scale(const double* scale) { (void)scale; }                  // scale: [m] validated by the caller, or NULL
-    virtual bool takes_family_rho() const { return false; }                           // shared-matrix batches only: one factor, hence one rho to move
-    int family_rho = 0;                                                               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule below
-    virtual bool takes_equilibration() const { return false; }                        // shared-matrix batches only
-    virtual void set_equilibration(int passes) { (void)passes; }                      // passes: 0..50 validated by the caller
-    std::vector<int> eq_kd, eq_ke;                                                    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
-    virtual bool takes_warm_start() const { return false; }                           // shared-matrix batches only: z and y stay on the handle between solves
-    int warm_start = 0;                                                               // qps_set_shared_warm_start: 0 z = y = 0, 1 the stored (z, y), 2 z = A x and the stored y
-    virtual void set_dual(const double* z, const double* y) { (void)z; (void)y; }     // [count][m] each, finite (validated by the caller); NULL keeps that array
-};
-
-// Ruiz equilibration of the shared-matrix batches with exact powers of two (qps_set_shared_equilibration).  The step for a norm v = f 2^e, f in [0.5, 1), is
-// -floor(e / 2): the power of two nearest to 1 / sqrt(v) on a log scale; 0 for v = 0.  Exponents stay in [-13, 13] (OSQP's [1e-4, 1e4]).
-constexpr int EQUIL_CLAMP = 13;
-inline int equil_step(double v) {
-    if (!(v > 0.0)) return 0;
-    int e; (void)std::frexp(v, &e);
-    return -(int)std::floor(e / 2.0);
-}
-// the range check: every non-zero scaled matrix entry has to stay a normal number of the handle's type
-template <typename T> inline void equil_check_range(double hi, double lo) {
-    if (hi > (double)std::numeric_limits<T>::max() || lo < (double)std::numeric_limits<T>::min()) {
-        char b[256];
-        snprintf(b, sizeof b, "qps_set_shared_equilibration: a scaled matrix entry would leave the normal range of the handle's type (largest %.3g, smallest non-zero %.3g, "
-                              "range %.3g .. %.3g); the handle is unchanged", hi, lo, (double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max());
-        throw QpsError(QPS_ERR_UNSUPPORTED, b);
-    }
-}
-
-// Family-wide adaptive rho of the shared-matrix batches (qps_set_shared_adaptive_rho): the proposal of SolveQuadraticProgram.jl:92-96 with the four norms taken from
-// the worst columns still running after this check -- bp = argmax normResPrim / maxNormPrim, bd = argmax normResDual / maxNormDual (lowest index on ties, a NaN
-// quotient never wins against a number).  res: 8 doubles per column as k_shared_decide leaves them ([0..3] the four norms).  No running column: rhorho stays.
-// With one column this is k_check_decide's expression; a NaN proposal stays NaN and never passes the switch test of :47.
-inline double family_rho_proposal(const double* res, const std::vector<int>& active, int count, double rho, double rhorho) {
-    int bp = -1, bd = -1; double qp = 0, qd = 0;
-    for (int b = 0; b < count; ++b) {
-        if (!active[b]) continue;
-        const double* r = res + 8 * b;
-        const double p = r[0] / r[2], d = r[1] / r[3];
-        if (bp < 0 || (std::isnan(qp) && !std::isnan(p)) || p > qp) { bp = b; qp = p; }
-        if (bd < 0 || (std::isnan(qd) && !std::isnan(d)) || d > qd) { bd = b; qd = d; }
-    }
-    if (bp < 0) return rhorho;
-    const double MIN_VAL_RHO = 1e-3, MAX_VAL_RHO = 1e6;                                     // :81-82
-    const double numeratorVal = res[8 * bp + 0] * res[8 * bd + 3];                          // normResPrim_bp * maxNormDual_bd
-    const double denominatorVal = res[8 * bd + 1] * res[8 * bp + 2];                        // normResDual_bd * maxNormPrim_bp
-    const double t = rho * std::sqrt(numeratorVal / denominatorVal);
-    return t > MAX_VAL_RHO ? MAX_VAL_RHO : (t < MIN_VAL_RHO ? MIN_VAL_RHO : t);
-}
-
 template <typename T> struct BatchedDenseSolver : BatchSolverBase {
     StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
     int NP = 0, MP = 0, nb = 0, slabs = 0, rpw = 0, part_tiles = 0;
@@ -854,651 +782,11 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
 };
 
 // =================================================================================================================
-// Shared-matrix batch: `count` QPs on ONE P and ONE A that differ in q, l, u only (an MPC horizon re-solved every sample, a regularisation
-// path, a scenario sweep).  One copy of every matrix, one factorisation, one sweep matrix with a single inverted block; the state lives in
-// 16-column panels and every product of the loop is a row-major matrix times panels on the MFMA pipe (k_shared.hip), so a matrix is read once
-// per launch whatever `count` is.  Per iteration: A' (a row-major copy of the transpose), the lower and the upper triangle of S, A.
-// rho is common (a common factor needs a common rho): fixed, or moved for the whole family by qps_set_shared_adaptive_rho; every column keeps its own check, flag, stopping iteration and residuals, and a column
-// that stopped is frozen by the active mask, exactly as BatchedDenseSolver does.
-// =================================================================================================================
-template <typename T> inline int shared_batch_max_np() { return 16 * 512 * VecOf<T>::N; }   // whole-factor explicit inverse: 16384 fp64 / 32768 fp32 (k_trsv.hip)
-
-template <typename T> struct SharedBatchSolver : BatchSolverBase {
-    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
-    int NP = 0, MP = 0, CP = 0, npanel = 0, nb = 0;
-    T *A = nullptr, *At = nullptr, *P = nullptr, *PI = nullptr, *AA = nullptr, *M = nullptr, *S = nullptr, *tmp = nullptr, *dinv = nullptr;
-    T *q = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *xp = nullptr, *xx = nullptr, *tt = nullptr, *yv = nullptr, *z = nullptr, *zp = nullptr,
-      *y = nullptr, *w = nullptr, *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
-    int* fail = nullptr; int* d_active = nullptr; int* h_int = nullptr;
-    unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
-    bool have_AA = false, factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0, cat_chk = 0, cat_fac = 0, cat_switch = 0, cat_start = 0;
-    std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
-    // Per-row rho scale (qps_set_shared_rho_scale): row i runs with rho_i = rho s_i.  Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so
-    // M = PI + rho Ws'Ws comes out of the same symmetric product and a change of the base rho alone only re-assembles; rs_rho / rs_rho1 hold rho_i and 1 / rho_i
-    // (MP long, padding rows: scale 1), formed in double and rounded once, for the base rho rs_base (0: stale).  All four buffers exist only while a scale is set.
-    std::vector<double> rho_scale; T *Ws = nullptr, *rs_sqrt = nullptr, *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
-    // Equilibration (qps_set_shared_equilibration): while it is on, P, A, At hold D P D, E A D, D A' E and q, l, u hold D q, E l, E u -- scaled in place by exact
-    // powers of two, undone in place when it is cleared -- and kd / ke (NP / MP ints, padding 0) are the exponents on the device; the loop kernels run as they are.
-    int *kd = nullptr, *ke = nullptr;
-
-    SharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_) {
-        device = dev; n = n_; m = m_; count = cnt;
-        HIPC(hipSetDevice(device));
-        st = prof.st = lease.acquire(device);
-        NP = roundup(n, 64); MP = roundup(m, 64); CP = roundup(count, 16); npanel = CP / 16;
-        nb = pick_nb<T>(32768, NP);   // one inverted block over the whole factor
-        const int64_t nn = (int64_t)NP * NP, mn = (int64_t)MP * NP, pn = (int64_t)CP * NP, pm = (int64_t)CP * MP;
-        A = mem.dalloc<T>(mn, st); At = mem.dalloc<T>(mn, st); P = mem.dalloc<T>(nn, st); PI = mem.dalloc<T>(nn, st); AA = mem.dalloc<T>(nn, st);
-        M = mem.dalloc<T>(nn, st); S = mem.dalloc<T>(nn, st); tmp = mem.dalloc<T>(nn, st); dinv = mem.dalloc<T>((int64_t)(NP / 64) * 4096, st);
-        q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); xx = mem.dalloc<T>(pn, st); tt = mem.dalloc<T>(pn, st);
-        yv = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
-        l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st);
-        w = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
-        for (T* v : {z, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)pm, st));                 // the state qps_set_shared_warm_start continues from is defined from creation on
-        fail = mem.dalloc<int>(4, st); d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
-        slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
-        stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
-        // algorithmic bytes per launch: the matrix once, the panels it reads and writes
-        const double s = sizeof(T), c = CP;
-        cat_atw = prof.category("shared: A'w + rhs (MFMA panels)", s * ((double)m * n + c * (m + 3.0 * n)));
-        cat_fwd = prof.category("shared: forward sweep (MFMA panels)", s * ((double)n * (n + 1) / 2 + 2.0 * c * n));
-        cat_bwd = prof.category("shared: backward sweep + x (MFMA panels)", s * ((double)n * (n + 1) / 2 + 5.0 * c * n));
-        cat_pass = prof.category("shared: A x~ + row updates (MFMA panels)", s * ((double)m * n + c * (n + 8.0 * m)));
-        cat_chk = prof.category("shared: check (A x, P x, A'y, norms)", s * (2.0 * m * n + (double)n * n + c * (8.0 * n + 6.0 * m)));
-        cat_fac = prof.category("shared: factorisation at setup", s * ((double)m * n + 4.0 * n * n));
-        cat_switch = prof.category("shared: rho switch (assemble, Cholesky, w)", s * (3.0 * n * n + 3.0 * c * m));
-        cat_start = prof.category("shared: warm start (w, or A x -> z, w)", s * 3.0 * c * m);
-    }
-    ~SharedBatchSolver() override {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(st);
-        prof.release_events();
-    }
-    // host [count][len] doubles -> panels (padding rows and columns zero); ordered on the stream, the host array is free when this returns
-    void put_panels(const double* h, T* d, int64_t len, int rowsP) {
-        HIPC(hipMemsetAsync(d, 0, sizeof(T) * (size_t)CP * rowsP, st));
-        if (!up) up.reset(new StagedUploader(st));   // its pinned double buffer lives as long as the handle: every solve uploads warm starts
-        up->copy(stage, h, sizeof(double) * (size_t)count * (size_t)len);
-        to_panels<T>(st, stage, count, (int)len, rowsP, d);
-        HIPC(hipStreamSynchronize(st));
-    }
-    void get_panels(const T* d, double* h, int64_t len, int rowsP) {
-        from_panels<T>(st, d, count, (int)len, rowsP, stage);
-        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count * (size_t)len, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    void load(const double* Ph, int64_t ldp, const double* Ah, int64_t lda, const double* qh, const double* lh, const double* uh) {
-        upload_matrix_panels<T>(st, device, Ph, ldp, (int)n, (int)n, P, NP);
-        upload_matrix_panels<T>(st, device, Ah, lda, (int)m, (int)n, A, NP);
-        transpose_rowmajor<T>(st, A, NP, MP, NP, At, MP);   // row-major A': every product of the loop is "row-major matrix x panel"
-        update_vectors(qh, lh, uh);
-    }
-    bool update_vectors(const double* qh, const double* lh, const double* uh) override {
-        HIPC(hipSetDevice(device));
-        if (qh) { put_panels(qh, q, n, NP); if (kd) panel_rowscale<T>(st, q, kd, 1, NP, npanel, q); }          // q~ = D q
-        if (lh) { put_panels(lh, l, m, MP); if (kd) panel_rowscale<T>(st, l, ke, 1, MP, npanel, l); }          // l~ = E l, u~ = E u (infinite stays infinite)
-        if (uh) { put_panels(uh, u, m, MP); if (kd) panel_rowscale<T>(st, u, ke, 1, MP, npanel, u); }
-        return true;   // the factor depends on P, A, rho, sigma only: it stays valid
-    }
-    void get_dual(double* zh, double* yh) override {
-        HIPC(hipSetDevice(device));
-        if (!kd) {
-            if (zh) get_panels(z, zh, m, MP);
-            if (yh) get_panels(y, yh, m, MP);
-            return;
-        }
-        // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
-        if (zh) { panel_rowscale<T>(st, z, ke, -1, MP, npanel, Ax); get_panels(Ax, zh, m, MP); }
-        if (yh) { panel_rowscale<T>(st, y, ke, 1, MP, npanel, Ax); get_panels(Ax, yh, m, MP); }
-    }
-    bool takes_warm_start() const override { return true; }
-    void set_dual(const double* zh, const double* yh) override {   // the counterpart of get_dual: z~ = E z, y~ = E^-1 y
-        HIPC(hipSetDevice(device));
-        if (zh) { put_panels(zh, z, m, MP); if (kd) panel_rowscale<T>(st, z, ke, 1, MP, npanel, z); }
-        if (yh) { put_panels(yh, y, m, MP); if (kd) panel_rowscale<T>(st, y, ke, -1, MP, npanel, y); }
-        HIPC(hipStreamSynchronize(st));
-    }
-    bool takes_equilibration() const override { return true; }
-    // the matrices and every vector the handle keeps between calls, in place: *= 2^(+-k) by the exponents in kd / ke
-    void apply_equilibration(int sign) {
-        scale_two_sided<T>(st, P, NP, NP, kd, kd, sign);
-        scale_two_sided<T>(st, A, MP, NP, ke, kd, sign);
-        scale_two_sided<T>(st, At, NP, MP, kd, ke, sign);
-        panel_rowscale<T>(st, q, kd, sign, NP, npanel, q);
-        for (T* v : {l, u, z}) panel_rowscale<T>(st, v, ke, sign, MP, npanel, v);
-        panel_rowscale<T>(st, y, ke, -sign, MP, npanel, y);
-    }
-    void set_equilibration(int passes) override {
-        HIPC(hipSetDevice(device));
-        HIPC(hipStreamSynchronize(st));
-        const bool was_on = kd != nullptr;
-        if (was_on) apply_equilibration(-1);                       // the caller's matrices again, bit for bit
-        int *nkd = nullptr, *nke = nullptr; std::vector<int> hkd, hke;
-        if (passes > 0) {
-            nkd = mem.dalloc<int>(NP, st); nke = mem.dalloc<int>(MP, st);
-            double* nrm = mem.dalloc<double>(3 * (int64_t)NP + 2 * (int64_t)MP, st);
-            double *cnP = nrm, *cnA = nrm + NP, *rn = nrm + 2 * NP, *loP = nrm + 2 * NP + MP, *loA = nrm + 3 * NP + MP;
-            for (int k = 0; k < passes; ++k) {                     // Jacobi: every norm of a pass reads the exponents from before the pass
-                equil_rownorm<T>(st, P, NP, NP, nkd, nkd, cnP, nullptr);        // P is symmetric and At is kept row-major: every norm is a row reduction
-                equil_rownorm<T>(st, At, NP, MP, nkd, nke, cnA, nullptr);
-                equil_rownorm<T>(st, A, MP, NP, nke, nkd, rn, nullptr);
-                equil_update(st, NP, cnP, cnA, nkd);
-                equil_update(st, MP, rn, nullptr, nke);
-            }
-            equil_rownorm<T>(st, P, NP, NP, nkd, nkd, cnP, loP);
-            equil_rownorm<T>(st, A, MP, NP, nke, nkd, rn, loA);
-            std::vector<double> h(3 * (size_t)NP + 2 * (size_t)MP);
-            hkd.resize(NP); hke.resize(MP);
-            HIPC(hipMemcpyAsync(h.data(), nrm, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
-            HIPC(hipMemcpyAsync(hkd.data(), nkd, sizeof(int) * NP, hipMemcpyDeviceToHost, st));
-            HIPC(hipMemcpyAsync(hke.data(), nke, sizeof(int) * MP, hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-            mem.release(nrm);
-            double hi = 0, lo = INFINITY;
-            for (int i = 0; i < NP; ++i) { hi = std::fmax(hi, h[i]); lo = std::fmin(lo, h[2 * (size_t)NP + MP + i]); }
-            for (int i = 0; i < MP; ++i) { hi = std::fmax(hi, h[2 * (size_t)NP + i]); lo = std::fmin(lo, h[3 * (size_t)NP + MP + i]); }
-            try { equil_check_range<T>(hi, lo); }
-            catch (...) {
-                mem.release(nkd); mem.release(nke);
-                if (was_on) { apply_equilibration(1); HIPC(hipStreamSynchronize(st)); }   // the previous scaling, its factor and its cached product stay
-                throw;
-            }
-        }
-        mem.release(kd); mem.release(ke);
-        kd = nkd; ke = nke;
-        eq_kd.assign(hkd.begin(), hkd.begin() + (passes > 0 ? n : 0)); eq_ke.assign(hke.begin(), hke.begin() + (passes > 0 ? m : 0));
-        if (kd) apply_equilibration(1);
-        if (Ws) scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);         // the per-row rho scale reads the new A
-        HIPC(hipStreamSynchronize(st));
-        factor_valid = false; have_AA = false;                     // the cached product and the factor belong to the previous matrices
-    }
-    bool takes_rho_scale() const override { return true; }
-    bool takes_family_rho() const override { return true; }
-    void set_rho_scale(const double* s) override {
-        HIPC(hipSetDevice(device));
-        HIPC(hipStreamSynchronize(st));
-        if (!s) {
-            for (T** v : {&Ws, &rs_sqrt, &rs_rho, &rs_rho1}) { mem.release(*v); *v = nullptr; }
-            rho_scale.clear();
-        } else {
-            if (!Ws) Ws = mem.dalloc<T>((int64_t)MP * NP, st);
-            if (!rs_sqrt) rs_sqrt = mem.dalloc<T>(MP, st);
-            if (!rs_rho) rs_rho = mem.dalloc<T>(MP, st);
-            if (!rs_rho1) rs_rho1 = mem.dalloc<T>(MP, st);
-            std::vector<T> h((size_t)MP, T(1));
-            for (int64_t i = 0; i < m; ++i) h[i] = (T)std::sqrt(s[i]);
-            if (!up) up.reset(new StagedUploader(st));
-            up->copy(rs_sqrt, h.data(), sizeof(T) * (size_t)MP);
-            scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);
-            HIPC(hipStreamSynchronize(st));
-            rho_scale.assign(s, s + m);
-        }
-        factor_valid = false; have_AA = false; rs_base = 0;   // the cached product and the factor belong to the previous scale
-    }
-    void push_row_rho(double rho) {   // rho_i and 1 / rho_i for this base rho
-        if (rs_base == rho) return;
-        std::vector<T> h((size_t)MP), h1((size_t)MP);
-        for (int i = 0; i < MP; ++i) { const double r = rho * (i < m ? rho_scale[i] : 1.0); h[i] = (T)r; h1[i] = (T)(1.0 / r); }
-        up->copy(rs_rho, h.data(), sizeof(T) * (size_t)MP);
-        up->copy(rs_rho1, h1.data(), sizeof(T) * (size_t)MP);
-        HIPC(hipStreamSynchronize(st));
-        rs_base = rho;
-    }
-    // LinSysSolInit once for all columns: LinearSystemSolvers.jl:110-122 + factorisation, sweep matrix with one inverted block
-    void factorize(double rho, double sigma, bool rebuild_all) {
-        const bool rebuild = rebuild_all || !have_AA;
-        const DenseChol<T> c{st, (int)n, NP, MP, P, rho_scale.empty() ? A : Ws, PI, AA, M, S, tmp, dinv, fail};   // A'A, or A' diag(s) A = Ws'Ws
-        factor_valid = false;
-        HIPC(hipMemsetAsync(fail, 0, sizeof(int) * 4, st));
-        c.form(sigma, rho, rebuild, rebuild);
-        have_AA = true;
-        c.factor(nb);
-        char ctx[128]; snprintf(ctx, sizeof ctx, "rho=%g, sigma=%g; factorisation #%d of this handle", rho, sigma, ++num_factorizations);
-        c.check("P + sigma I + rho A'A", ctx, h_int);
-        factor_valid = true; fac_rho = rho; fac_sigma = sigma;
-    }
-    PanelArgs<T> product_args(const T* Mat, int64_t ld, int rows, int K, const T* B, T* out) const {
-        PanelArgs<T> a; a.Mat = Mat; a.ld = ld; a.rows = rows; a.K = K; a.B = B; a.npanel = npanel; a.out = out; a.active = d_active;
-        return a;
-    }
-
-    void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
-        HIPC(hipSetDevice(device));
-        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: adptRho is not supported (one factor serves every column, so the per-problem rule cannot run; "
-                                                           "qps_set_shared_adaptive_rho turns on the family-wide rule)");
-        if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: polishing is not supported");
-        if (p.trsvBlock != 0 && p.trsvBlock < n)
-            throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: trsvBlock must be 0 or >= n (the sweeps run over one inverted block covering the whole factor)");
-        if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "shared-matrix batch: QPS_LINSYS_CHOLESKY only");
-        const double t0 = now_s();
-        if (family_rho && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
-        double rho = p.rho, rhorho = rho;                                                           // :43; rho moves under the family rule only
-        const double sigma = p.sigma, alpha = p.alpha;
-        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
-        const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
-        const bool scaled = !rho_scale.empty();
-        if (scaled) push_row_rho(rho);
-        if (!reuse) { ProfScope ps(prof, cat_fac, 1); factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma); }   // :36
-        put_panels(xh, x, n, NP);
-        if (kd) panel_rowscale<T>(st, x, kd, -1, NP, npanel, x);                                    // warm start in the scaled variables: x~ = D^-1 x
-        for (T* v : {xp, xx, tt, yv}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * NP, st));  // :38
-        const int warm = warm_start;
-        if (warm == 0) { for (T* v : {z, zp, y, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st)); }   // :39-41
-        else { for (T* v : {zp, w}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * MP, st)); }  // z (mode 1) and y stay: iteration 1 overwrites zp before a check reads it
-        std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
-        std::vector<double> resP(count, NAN), resD(count, NAN);
-        for (int b = 0; b < count; ++b) active[b] = 1;
-        auto push_active = [&] {
-            for (int b = 0; b < CP; ++b) h_int[b] = active[b];
-            HIPC(hipMemcpyAsync(d_active, h_int, sizeof(int) * CP, hipMemcpyHostToDevice, st));
-            HIPC(hipStreamSynchronize(st));   // the pinned staging is reused
-        };
-        push_active();
-        if (warm == 1) {                                                                            // w = rho_i z - y for this solve's rho: what the row update would have left
-            ProfScope ps(prof, cat_start, 1);
-            panel_w<T>(st, z, y, d_active, scaled ? rs_rho : nullptr, (T)rho, MP, npanel, w);
-        } else if (warm == 2) {                                                                     // OSQP's warm_start(x, y): z = A x~ without projection, w with the stored y
-            ProfScope ps(prof, cat_start, 1);
-            PanelArgs<T> a_st = product_args(A, NP, MP, NP, x, nullptr);
-            a_st.z = z; a_st.y = y; a_st.w = w; a_st.rho = (T)rho; a_st.rho_row = scaled ? rs_rho : nullptr;
-            shared_panel<T>(st, SharedPanelOp::start_z, a_st);
-        }
-        const double t1 = now_s();
-        PanelArgs<T> a_rhs = product_args(At, MP, NP, MP, w, tt); a_rhs.x = x; a_rhs.q = q; a_rhs.sigma = (T)sigma;
-        PanelArgs<T> a_fwd = product_args(S, NP, NP, NP, tt, yv);
-        PanelArgs<T> a_bwd = product_args(S, NP, NP, NP, yv, xx); a_bwd.x = x; a_bwd.xp = xp; a_bwd.alpha = (T)alpha;
-        PanelArgs<T> a_row = product_args(A, NP, MP, NP, xx, nullptr);
-        a_row.z = z; a_row.zp = zp; a_row.y = y; a_row.w = w; a_row.l = l; a_row.u = u; a_row.alpha = (T)alpha; a_row.rho = (T)rho;
-        a_row.rho_row = rs_rho; a_row.rho1_row = rs_rho1;
-        const SharedPanelOp op_row = scaled ? SharedPanelOp::rows_zy_scaled : SharedPanelOp::rows_zy;
-        const PanelArgs<T> a_ax = product_args(A, NP, MP, NP, x, Ax), a_px = product_args(P, NP, NP, NP, x, Px), a_aty = product_args(At, MP, NP, MP, y, Aty);
-        int nactive = count;
-        std::vector<int> nref(count, 0); std::vector<double> rho_col(count, rho), prop_col(count, rho); double tref = 0;
-        for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
-            if (family_rho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {         // :47, once for the family
-                const double ta = now_s();
-                {
-                    ProfScope ps(prof, cat_switch, 1);
-                    rho = rhorho;
-                    factorize(rho, sigma, false);                                                   // changedΡ: A'A is kept, assembly and Cholesky only
-                    if (scaled) push_row_rho(rho);
-                    a_row.rho = (T)rho;
-                    panel_w<T>(st, z, y, d_active, scaled ? rs_rho : nullptr, (T)rho, MP, npanel, w);   // w held rho z - y of the previous rho
-                }
-                for (int b = 0; b < count; ++b) if (active[b]) { ++nref[b]; rho_col[b] = rho; }
-                HIPC(hipStreamSynchronize(st));                                                     // tRefactor: host wall time until the device has finished the switch
-                tref += now_s() - ta;
-            }
-            const int lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one launch of each kernel in 50 iterations
-            { ProfLaunchScope ps(prof, cat_atw, lvl); shared_panel<T>(st, SharedPanelOp::rhs, a_rhs); }          // LinearSystemSolvers.jl:134-136
-            { ProfLaunchScope ps(prof, cat_fwd, lvl); shared_panel<T>(st, SharedPanelOp::forward, a_fwd); }      // :137, L y = t
-            { ProfLaunchScope ps(prof, cat_bwd, lvl); shared_panel<T>(st, SharedPanelOp::backward_x, a_bwd); }   // :137, L' x~ = y; SolveQuadraticProgram.jl:56-57
-            { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, op_row, a_row); }     // :139; SolveQuadraticProgram.jl:59-61
-            if (ii % p.numItrConv != 0) continue;                                                   // :63
-            {
-                ProfScope ps(prof, cat_chk, 2);
-                HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long) * (size_t)CP, st));
-                shared_panel<T>(st, SharedPanelOp::product, a_ax);                                  // mA * vX
-                shared_panel<T>(st, SharedPanelOp::product, a_px);                                  // mP * vX
-                shared_panel<T>(st, SharedPanelOp::product, a_aty);                                 // mA' * vY
-                shared_check<T>(st, (int)n, (int)m, NP, MP, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho, kd, ke);   // :64
-            }
-            HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-            prof.harvest();
-            bool any_done = false;
-            for (int b = 0; b < count; ++b) {
-                if (!active[b]) continue;
-                const double* r = res_host + 8 * b;
-                resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
-                if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
-            }
-            if (family_rho) {
-                rhorho = family_rho_proposal(res_host, active, count, rho, rhorho);
-                for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = rhorho;
-            }
-            if (any_done && nactive > 0) push_active();
-        }
-        HIPC(hipStreamSynchronize(st));
-        prof.harvest();
-        const double t2 = now_s();
-        if (kd) { panel_rowscale<T>(st, x, kd, 1, NP, npanel, Px); get_panels(Px, xh, n, NP); }      // x = D x~ (through the check's scratch panel)
-        else get_panels(x, xh, n, NP);
-        for (int b = 0; b < count && infos; ++b) {
-            qps_info& in = infos[b];
-            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
-            in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
-            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
-            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
-            in.trsvBlock = nb; in.sweepVariant = 3; in.sweepGaveUp = 0; in.cgExplicit = 0;
-        }
-    }
-};
-
-// =================================================================================================================
-// Sparse shared-matrix batch: `count` QPs on ONE sparse P and ONE sparse A (a lasso / SVM regularisation path, a scenario sweep on a sparse model).
-// The linear system is the sparse L D L' of the KKT matrix (k_ldl.hip): ordering and symbolic factor once at creation (host only), ONE numeric
-// factorisation per (rho, sigma), and every iteration runs the level-scheduled sweeps on 16-column panels -- the index and value of a factor entry are
-// loaded once for 16 QPs, the launch chain is paid once per batch.  The check's A x, P x, A'y are CSR x panel products (k_csr_panel.hip).
-// rho is common: fixed, or moved for the whole family (qps_set_shared_adaptive_rho); every column keeps its own check, flag, stopping iteration and residuals and
-// is frozen by the active mask, as in SharedBatchSolver.
-// =================================================================================================================
-struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
-    LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;
-};
-template <typename T> struct SparseSharedBatchSolver : BatchSolverBase {
-    StreamLease lease; DeviceOwner mem; hipStream_t st = nullptr;   // destroyed in reverse: buffers, then the stream lease, then the base's Profiler
-    int CP = 0, npanel = 0;
-    std::unique_ptr<SparseLdl<T>> ldl;
-    CsrPanelMatrix<T> P, A, At;
-    T *q = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *xp = nullptr, *z = nullptr, *zp = nullptr, *y = nullptr, *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
-    int* d_active = nullptr; int* h_int = nullptr;
-    unsigned long long* slots = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
-    bool factor_valid = false; double fac_rho = 0, fac_sigma = 0; int num_factorizations = 0;
-    LdlPanelProf pf; int cat_chk = 0, cat_fac = 0, cat_switch = 0, cat_start = 0;
-    std::unique_ptr<StagedUploader> up;   // (declared after the lease: its events go before the stream does)
-    // Per-row rho scale (qps_set_shared_rho_scale): rho_i = rho s_i and 1 / rho_i by the caller's row (m long), formed in double and rounded once, for the base
-    // rho rs_base (0: stale); the factor object reads them in its numeric factorisation and panel kernels.  They exist only while a scale is set.
-    std::vector<double> rho_scale; T *rs_rho = nullptr, *rs_rho1 = nullptr; double rs_base = 0;
-    // Equilibration (qps_set_shared_equilibration): the exponents come from the host copy of the canonical CSC arrays (values rounded to T); while it is on, the
-    // factor's value array and the three CSR value arrays of the check hold the scaled entries, q, l, u hold D q, E l, E u, and kd / ke (n / m ints) are the exponents
-    // on the device.  Ordering, symbolic factor and every index array stay as they are.
-    std::vector<int64_t> hPcp, hPri, hAcp, hAri; std::vector<double> hPnz, hAnz;
-    int *kd = nullptr, *ke = nullptr;
-
-    SparseSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, SparseSharedInput&& in, const double* qh, const double* lh, const double* uh) {
-        device = dev; n = n_; m = m_; count = cnt;
-        HIPC(hipSetDevice(device));
-        st = prof.st = lease.acquire(device);
-        CP = roundup(count, 16); npanel = CP / 16;
-        up.reset(new StagedUploader(st));
-        layout::CsrHost Ph, Ah, Ath;
-        try {
-            Ph = layout::csc_as_transposed_csr(n, n, in.Pcp, in.Pri, in.Pnz);      // P: CSC == CSR (symmetric, full storage)
-            layout::csc_to_csr_pair(m, n, in.Acp, in.Ari, in.Anz, Ah, Ath);        // rows of A by a counting sort; rows of A' are the columns of A
-        } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
-        P = upload_csr(Ph); A = upload_csr(Ah); At = upload_csr(Ath);
-        const int64_t pnnz = (int64_t)in.Pnz.size(), annz = (int64_t)in.Anz.size();
-        const int64_t nnzL = (int64_t)in.sym.ci.size(); const int N = in.sym.N, Ns = in.sym.Ns, ldt = in.sym.ldt;
-        ldl = make_sparse_ldl<T>(st, std::move(in.sym), in.Pnz.data(), pnnz, in.Anz.data(), annz);
-        ldl->panels_prepare(npanel, in.spr);
-        hPcp = std::move(in.Pcp); hPri = std::move(in.Pri); hPnz = std::move(in.Pnz); hAcp = std::move(in.Acp); hAri = std::move(in.Ari); hAnz = std::move(in.Anz);
-        const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
-        q = mem.dalloc<T>(pn, st); x = mem.dalloc<T>(pn, st); xp = mem.dalloc<T>(pn, st); Px = mem.dalloc<T>(pn, st); Aty = mem.dalloc<T>(pn, st);
-        l = mem.dalloc<T>(pm, st); u = mem.dalloc<T>(pm, st); z = mem.dalloc<T>(pm, st); zp = mem.dalloc<T>(pm, st); y = mem.dalloc<T>(pm, st); Ax = mem.dalloc<T>(pm, st);
-        for (T* v : {z, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)pm, st));                 // the state qps_set_shared_warm_start continues from is defined from creation on
-        d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
-        slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
-        stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
-        // algorithmic bytes per iteration (check: per check), counted as SparseLdl::bytes_per_solve does: every factor entry's index and value once per panel,
-        // the lines it gathers and the vectors read and written once per column
-        const double s = sizeof(T), c = CP, np = npanel, Nd = N, ents = (double)nnzL;
-        pf.prof = &prof;
-        pf.cat_rhs = prof.category("sparse shared: rhs (panels)", 4.0 * Nd * np + s * c * (2.0 * n + 2.0 * m + Nd));
-        pf.cat_fwd = prof.category("sparse shared: forward levels (panels)", np * ents * (s + 4) + s * c * (ents + 2.0 * Nd));
-        pf.cat_tail = prof.category("sparse shared: dense tail (MFMA panels)", s * ((double)ldt * (ldt + 1) + 6.0 * c * ldt));
-        pf.cat_bwd = prof.category("sparse shared: backward levels (panels)", np * ents * (s + 4) + s * c * (ents + 3.0 * Ns));
-        pf.cat_post = prof.category("sparse shared: post + update (panels)", 4.0 * Nd * np + s * c * (2.0 * Nd + 5.0 * n + 8.0 * m));
-        cat_chk = prof.category("sparse shared: check (A x, P x, A'y, norms)", np * (2.0 * annz + pnnz) * (s + 4) + s * c * ((2.0 * annz + pnnz) + 8.0 * n + 6.0 * m));
-        cat_fac = prof.category("sparse shared: factorisation at setup", (s + 4) * ents + s * (pnnz + annz));
-        cat_switch = prof.category("sparse shared: rho switch (numeric L D L')", (s + 4) * ents + s * (pnnz + annz));
-        cat_start = prof.category("sparse shared: warm start (A x -> z)", np * annz * (s + 4) + s * c * (annz + m));
-        update_vectors(qh, lh, uh);
-    }
-    ~SparseSharedBatchSolver() override {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(st);
-        prof.release_events();
-    }
-    CsrPanelMatrix<T> upload_csr(const layout::CsrHost& h) {
-        CsrPanelMatrix<T> M; M.rows = h.nrows;
-        int* rp = mem.dalloc<int>((int64_t)h.rp.size(), st); int* ci = mem.dalloc<int>((int64_t)h.ci.size(), st); T* va = mem.dalloc<T>((int64_t)h.va.size(), st);
-        std::vector<T> v(h.va.begin(), h.va.end());
-        up->copy(rp, h.rp.data(), sizeof(int) * h.rp.size());
-        if (!h.ci.empty()) { up->copy(ci, h.ci.data(), sizeof(int) * h.ci.size()); up->copy(va, v.data(), sizeof(T) * v.size()); }
-        M.rp = rp; M.ci = ci; M.va = va; M.spr = csr_panel_spr((int64_t)h.ci.size(), h.nrows);
-        return M;
-    }
-    // host [count][len] doubles -> panels (padding columns zero); ordered on the stream, the host array is free when this returns
-    void put_panels(const double* h, T* d, int64_t len) {
-        HIPC(hipMemsetAsync(d, 0, sizeof(T) * (size_t)CP * (size_t)len, st));
-        up->copy(stage, h, sizeof(double) * (size_t)count * (size_t)len);
-        to_panels<T>(st, stage, count, (int)len, (int)len, d);
-        HIPC(hipStreamSynchronize(st));
-    }
-    void get_panels(const T* d, double* h, int64_t len) {
-        from_panels<T>(st, d, count, (int)len, (int)len, stage);
-        HIPC(hipMemcpyAsync(h, stage, sizeof(double) * (size_t)count * (size_t)len, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    bool update_vectors(const double* qh, const double* lh, const double* uh) override {
-        HIPC(hipSetDevice(device));
-        if (qh) { put_panels(qh, q, n); if (kd) panel_rowscale<T>(st, q, kd, 1, (int)n, npanel, q); }          // q~ = D q
-        if (lh) { put_panels(lh, l, m); if (kd) panel_rowscale<T>(st, l, ke, 1, (int)m, npanel, l); }          // l~ = E l, u~ = E u (infinite stays infinite)
-        if (uh) { put_panels(uh, u, m); if (kd) panel_rowscale<T>(st, u, ke, 1, (int)m, npanel, u); }
-        return true;   // the factor depends on P, A, rho, sigma only: it stays valid
-    }
-    void get_dual(double* zh, double* yh) override {
-        HIPC(hipSetDevice(device));
-        if (!kd) {
-            if (zh) get_panels(z, zh, m);
-            if (yh) get_panels(y, yh, m);
-            return;
-        }
-        // z = E^-1 z~, y = E y~ through the check's scratch panel: the state of the handle stays as the solve left it
-        if (zh) { panel_rowscale<T>(st, z, ke, -1, (int)m, npanel, Ax); get_panels(Ax, zh, m); }
-        if (yh) { panel_rowscale<T>(st, y, ke, 1, (int)m, npanel, Ax); get_panels(Ax, yh, m); }
-    }
-    bool takes_warm_start() const override { return true; }
-    void set_dual(const double* zh, const double* yh) override {   // the counterpart of get_dual: z~ = E z, y~ = E^-1 y
-        HIPC(hipSetDevice(device));
-        if (zh) { put_panels(zh, z, m); if (kd) panel_rowscale<T>(st, z, ke, 1, (int)m, npanel, z); }
-        if (yh) { put_panels(yh, y, m); if (kd) panel_rowscale<T>(st, y, ke, -1, (int)m, npanel, y); }
-        HIPC(hipStreamSynchronize(st));
-    }
-    bool takes_equilibration() const override { return true; }
-    // every value array and every vector the handle keeps between calls, in place: *= 2^(+-k) by the host exponents hd / he (device copies in kd / ke)
-    void apply_equilibration(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
-        const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
-        layout::CsrHost Ph = layout::csc_as_transposed_csr(n, n, hPcp, hPri, hPnz), Ah, Ath;
-        layout::csc_to_csr_pair(m, n, hAcp, hAri, hAnz, Ah, Ath);
-        // one exponent per entry, in the order of each value array: the factor's [P; A] in CSC order, then the CSR copies P, A, A'
-        std::vector<int> e((size_t)(2 * pnnz + 3 * annz));
-        int* eK = e.data(); int *eP = eK + pnnz + annz, *eA = eP + pnnz, *eAt = eA + annz;
-        for (int64_t j = 0; j < n; ++j) {
-            for (int64_t k = hPcp[j]; k < hPcp[j + 1]; ++k) eK[k] = hd[hPri[k]] + hd[j];
-            for (int64_t k = hAcp[j]; k < hAcp[j + 1]; ++k) eK[pnnz + k] = he[hAri[k]] + hd[j];
-        }
-        for (int r = 0; r < Ph.nrows; ++r) for (int k = Ph.rp[r]; k < Ph.rp[r + 1]; ++k) eP[k] = hd[r] + hd[Ph.ci[k]];
-        for (int r = 0; r < Ah.nrows; ++r) for (int k = Ah.rp[r]; k < Ah.rp[r + 1]; ++k) eA[k] = he[r] + hd[Ah.ci[k]];
-        for (int r = 0; r < Ath.nrows; ++r) for (int k = Ath.rp[r]; k < Ath.rp[r + 1]; ++k) eAt[k] = hd[r] + he[Ath.ci[k]];
-        int* de = mem.dalloc<int>((int64_t)e.size(), st);
-        if (!e.empty()) up->copy(de, e.data(), sizeof(int) * e.size());
-        ldl->rescale_values(de, sign);
-        scale_entries<T>(st, const_cast<T*>(P.va), de + pnnz + annz, sign, pnnz);
-        scale_entries<T>(st, const_cast<T*>(A.va), de + 2 * pnnz + annz, sign, annz);
-        scale_entries<T>(st, const_cast<T*>(At.va), de + 2 * pnnz + 2 * annz, sign, annz);
-        panel_rowscale<T>(st, q, kd, sign, (int)n, npanel, q);
-        for (T* v : {l, u, z}) panel_rowscale<T>(st, v, ke, sign, (int)m, npanel, v);
-        panel_rowscale<T>(st, y, ke, -sign, (int)m, npanel, y);
-        HIPC(hipStreamSynchronize(st));
-        mem.release(de);
-    }
-    void set_equilibration(int passes) override {
-        HIPC(hipSetDevice(device));
-        HIPC(hipStreamSynchronize(st));
-        // the rule of the dense handle on the host: norms in double from the values rounded to T, read through the exponents
-        std::vector<int> hd, he;
-        if (passes > 0) {
-            const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
-            std::vector<double> aP((size_t)pnnz), aA((size_t)annz), cn((size_t)n), rn((size_t)m);
-            for (int64_t k = 0; k < pnnz; ++k) aP[k] = std::fabs((double)(T)hPnz[k]);
-            for (int64_t k = 0; k < annz; ++k) aA[k] = std::fabs((double)(T)hAnz[k]);
-            hd.assign((size_t)n, 0); he.assign((size_t)m, 0);
-            double hi = 0, lo = INFINITY;
-            for (int pass = 0; pass <= passes; ++pass) {           // the last round only measures the range of the scaled entries
-                std::fill(cn.begin(), cn.end(), 0.0); std::fill(rn.begin(), rn.end(), 0.0);
-                hi = 0; lo = INFINITY;
-                for (int64_t j = 0; j < n; ++j) {
-                    for (int64_t k = hPcp[j]; k < hPcp[j + 1]; ++k) {
-                        const double v = std::ldexp(aP[k], hd[hPri[k]] + hd[j]);
-                        cn[j] = std::fmax(cn[j], v); hi = std::fmax(hi, v); if (v > 0) lo = std::fmin(lo, v);
-                    }
-                    for (int64_t k = hAcp[j]; k < hAcp[j + 1]; ++k) {
-                        const int64_t i = hAri[k];
-                        const double v = std::ldexp(aA[k], he[i] + hd[j]);
-                        cn[j] = std::fmax(cn[j], v); rn[i] = std::fmax(rn[i], v); hi = std::fmax(hi, v); if (v > 0) lo = std::fmin(lo, v);
-                    }
-                }
-                if (pass == passes) break;
-                for (int64_t j = 0; j < n; ++j) hd[j] = std::max(-EQUIL_CLAMP, std::min(EQUIL_CLAMP, hd[j] + equil_step(cn[j])));
-                for (int64_t i = 0; i < m; ++i) he[i] = std::max(-EQUIL_CLAMP, std::min(EQUIL_CLAMP, he[i] + equil_step(rn[i])));
-            }
-            equil_check_range<T>(hi, lo);                          // before anything is modified
-        }
-        if (kd) apply_equilibration(-1, eq_kd, eq_ke);             // the caller's values again, bit for bit
-        mem.release(kd); mem.release(ke); kd = ke = nullptr;
-        eq_kd = hd; eq_ke = he;
-        if (passes > 0) {
-            kd = mem.dalloc<int>(n, st); ke = mem.dalloc<int>(m, st);
-            up->copy(kd, hd.data(), sizeof(int) * (size_t)n);
-            up->copy(ke, he.data(), sizeof(int) * (size_t)m);
-            apply_equilibration(1, hd, he);
-        }
-        factor_valid = false;                                      // the numeric factor belongs to the previous values
-    }
-    bool takes_rho_scale() const override { return true; }
-    bool takes_family_rho() const override { return true; }
-    void set_rho_scale(const double* s) override {
-        HIPC(hipSetDevice(device));
-        HIPC(hipStreamSynchronize(st));
-        if (!s) {
-            ldl->set_row_rho(nullptr, nullptr);
-            for (T** v : {&rs_rho, &rs_rho1}) { mem.release(*v); *v = nullptr; }
-            rho_scale.clear();
-        } else {
-            if (!rs_rho) rs_rho = mem.dalloc<T>(m, st);
-            if (!rs_rho1) rs_rho1 = mem.dalloc<T>(m, st);
-            rho_scale.assign(s, s + m);
-            ldl->set_row_rho(rs_rho, rs_rho1);
-        }
-        factor_valid = false; rs_base = 0;   // the factor belongs to the previous scale
-    }
-    void push_row_rho(double rho) {   // rho_i and 1 / rho_i for this base rho
-        if (rs_base == rho) return;
-        std::vector<T> h((size_t)m), h1((size_t)m);
-        for (int64_t i = 0; i < m; ++i) { const double r = rho * rho_scale[i]; h[i] = (T)r; h1[i] = (T)(1.0 / r); }
-        up->copy(rs_rho, h.data(), sizeof(T) * (size_t)m);
-        up->copy(rs_rho1, h1.data(), sizeof(T) * (size_t)m);
-        HIPC(hipStreamSynchronize(st));
-        rs_base = rho;
-    }
-    void solve_batch(double* xh, const qps_params& p, qps_info* infos) override {
-        HIPC(hipSetDevice(device));
-        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: adptRho is not supported (one factor serves every column, so the per-problem rule cannot "
-                                                           "run; qps_set_shared_adaptive_rho turns on the family-wide rule)");
-        if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: polish is not supported");
-        if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_KKT_LDL) throw QpsError(QPS_ERR_UNSUPPORTED, "sparse shared-matrix batch: linsys must be QPS_LINSYS_AUTO or QPS_LINSYS_KKT_LDL");
-        const double t0 = now_s();
-        if (family_rho && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
-        double rho = p.rho, rhorho = rho;                                                           // :43; rho moves under the family rule only
-        const double sigma = p.sigma, alpha = p.alpha;
-        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
-        const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
-        if (!rho_scale.empty()) push_row_rho(rho);
-        if (!reuse) {                                                                               // :36: numeric factorisation, once for all columns
-            ProfScope ps(prof, cat_fac, 1);
-            factor_valid = false;
-            ++num_factorizations;
-            ldl->factorize(rho, sigma);
-            factor_valid = true; fac_rho = rho; fac_sigma = sigma;
-        }
-        put_panels(xh, x, n);
-        if (kd) panel_rowscale<T>(st, x, kd, -1, (int)n, npanel, x);                                // warm start in the scaled variables: x~ = D^-1 x
-        HIPC(hipMemsetAsync(xp, 0, sizeof(T) * (size_t)CP * (size_t)n, st));                        // :38
-        const int warm = warm_start;
-        if (warm == 0) { for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); }   // :39-41
-        else HIPC(hipMemsetAsync(zp, 0, sizeof(T) * (size_t)CP * (size_t)m, st));                   // z (mode 1) and y stay; the first right-hand side is built from them (rhs_ready)
-        if (warm == 2) { ProfScope ps(prof, cat_start, 1); csr_panel<T>(st, A, x, (int)n, z, (int)m, npanel); }   // OSQP's warm_start(x, y): z = A x~ without projection
-        std::vector<int> active(CP, 0), conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
-        std::vector<double> resP(count, NAN), resD(count, NAN);
-        for (int b = 0; b < count; ++b) active[b] = 1;
-        auto push_active = [&] {
-            for (int b = 0; b < CP; ++b) h_int[b] = active[b];
-            HIPC(hipMemcpyAsync(d_active, h_int, sizeof(int) * CP, hipMemcpyHostToDevice, st));
-            HIPC(hipStreamSynchronize(st));   // the pinned staging is reused
-        };
-        push_active();
-        const double t1 = now_s();
-        LdlPanelState<T> s; s.x = x; s.xp = xp; s.q = q; s.z = z; s.zp = zp; s.y = y; s.l = l; s.u = u; s.active = d_active; s.npanel = npanel;
-        int nactive = count; bool rhs_ready = false;
-        std::vector<int> nref(count, 0); std::vector<double> rho_col(count, rho), prop_col(count, rho); double tref = 0;
-        for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
-            if (family_rho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {         // :47, once for the family
-                const double ta = now_s();
-                {
-                    ProfScope ps(prof, cat_switch, 1);
-                    rho = rhorho;
-                    if (!rho_scale.empty()) push_row_rho(rho);                                      // the numeric factorisation reads rho_i
-                    factor_valid = false;
-                    ++num_factorizations;
-                    ldl->factorize(rho, sigma);                                                     // changedΡ: numeric only, on the frozen pattern
-                    factor_valid = true; fac_rho = rho;
-                    rhs_ready = false;                                                              // the right-hand side left behind holds 1 / rho of the previous rho
-                }
-                for (int b = 0; b < count; ++b) if (active[b]) { ++nref[b]; rho_col[b] = rho; }
-                HIPC(hipStreamSynchronize(st));                                                     // tRefactor: host wall time until the device has finished the switch
-                tref += now_s() - ta;
-            }
-            pf.lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one sample of each category in 50 iterations
-            ldl->iterate_panels(s, alpha, rho, sigma, rhs_ready, pf);                               // LinearSystemSolvers.jl:37-40, SolveQuadraticProgram.jl:56-61
-            rhs_ready = true;
-            if (ii % p.numItrConv != 0) continue;                                                   // :63
-            {
-                ProfScope ps(prof, cat_chk, 2);
-                HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long) * (size_t)CP, st));
-                csr_panel<T>(st, A, x, (int)n, Ax, (int)m, npanel);                                 // mA * vX
-                csr_panel<T>(st, P, x, (int)n, Px, (int)n, npanel);                                 // mP * vX
-                csr_panel<T>(st, At, y, (int)m, Aty, (int)n, npanel);                               // mA' * vY
-                shared_check<T>(st, (int)n, (int)m, (int)n, (int)m, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho, kd, ke);   // :64
-            }
-            HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-            prof.harvest();
-            bool any_done = false;
-            for (int b = 0; b < count; ++b) {
-                if (!active[b]) continue;
-                const double* r = res_host + 8 * b;
-                resP[b] = r[0]; resD[b] = r[1]; conv[b] = (int)r[5];
-                if (conv[b] != QPS_CONV_NUM_ITR) { active[b] = 0; iters[b] = ii; --nactive; any_done = true; }   // :66-68: x, z, y of this column are frozen from here on
-            }
-            if (family_rho) {
-                rhorho = family_rho_proposal(res_host, active, count, rho, rhorho);
-                for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = rhorho;
-            }
-            if (any_done && nactive > 0) push_active();
-        }
-        HIPC(hipStreamSynchronize(st));
-        prof.harvest();
-        const double t2 = now_s();
-        if (kd) { panel_rowscale<T>(st, x, kd, 1, (int)n, npanel, Px); get_panels(Px, xh, n); }      // x = D x~ (through the check's scratch panel)
-        else get_panels(x, xh, n);
-        for (int b = 0; b < count && infos; ++b) {
-            qps_info& in = infos[b];
-            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
-            in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
-            in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
-            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
-            in.trsvBlock = 0; in.sweepVariant = 0; in.sweepGaveUp = 0; in.cgExplicit = 0;
-        }
-    }
-};
-
-// =================================================================================================================
 // handle plumbing
 // =================================================================================================================
 struct Handle { SolverBase* impl = nullptr; std::vector<SolverBase*> batch; BatchSolverBase* fused_batch = nullptr; ProxQpBase* proxqp = nullptr; int64_t n = 0, m = 0; std::string err; };
+// what the qps_*_shared_* entry points ask of a handle: the shared-matrix family behind it, or nullptr
+SharedFamilyOps* shared_family_of(Handle* h) { return h && h->fused_batch ? h->fused_batch->shared_family() : nullptr; }
 
 int fail_with(Handle* h, int code, const std::string& msg) {
     g_last_error = msg;
@@ -1840,15 +1128,11 @@ QPS_API int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t 
         if (bad >= 0) { char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)bad); return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b); }
     }
     if (m == 0) return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch needs m >= 1 (without constraints the columns are independent linear solves)");
-    if (roundup(n, 64) > (dtype == QPS_F64 ? shared_batch_max_np<double>() : shared_batch_max_np<float>()))
+    if (roundup(n, 64) > shared_batch_max_np(dtype))
         return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch: n beyond the limit of the whole-factor explicit inverse (16384 fp64, 32768 fp32)");
     if (const int dc = require_device(device)) return dc;
     Handle* h = new Handle(); h->n = n; h->m = m;
-    int rc = guarded(nullptr, [&] {
-        auto load = [&](auto s) { s->load(P, ldp, A, lda, q, l, u); h->fused_batch = s.release(); };   // a unique_ptr: a throw while loading drops the solver
-        if (dtype == QPS_F64) load(std::make_unique<SharedBatchSolver<double>>(device, (int)count, n, m));
-        else load(std::make_unique<SharedBatchSolver<float>>(device, (int)count, n, m));
-    });
+    int rc = guarded(nullptr, [&] { h->fused_batch = make_dense_shared_batch(device, dtype, (int)count, n, m, P, ldp, A, lda, q, l, u); });
     if (rc != QPS_OK) { delete h; return rc; }
     *out = reinterpret_cast<qps_handle>(h);
     return QPS_OK;
@@ -1895,10 +1179,7 @@ QPS_API int32_t qps_create_csc_shared_batch(int64_t count, int64_t n, int64_t m,
     if (rc != QPS_OK) return rc;
     if (const int dc = require_device(device)) return dc;
     Handle* h = new Handle(); h->n = n; h->m = m;
-    rc = guarded(nullptr, [&] {
-        if (dtype == QPS_F64) h->fused_batch = new SparseSharedBatchSolver<double>(device, (int)count, n, m, std::move(in), q, l, u);
-        else h->fused_batch = new SparseSharedBatchSolver<float>(device, (int)count, n, m, std::move(in), q, l, u);
-    });
+    rc = guarded(nullptr, [&] { h->fused_batch = make_sparse_shared_batch(device, dtype, (int)count, n, m, std::move(in), q, l, u); });
     if (rc != QPS_OK) { delete h; return rc; }
     *out = reinterpret_cast<qps_handle>(h);
     return QPS_OK;
@@ -1910,23 +1191,23 @@ QPS_API int32_t qps_update_shared_vectors(qps_handle hh, const double* q, const 
     const int64_t c = h->fused_batch->count;
     if (q && !all_finite(q, c * h->n, false)) return fail_with(h, QPS_ERR_NOT_FINITE, "q contains NaN/Inf");
     if ((l && !all_finite(l, c * h->m, true)) || (u && !all_finite(u, c * h->m, true))) return fail_with(h, QPS_ERR_NOT_FINITE, "l/u contain NaN");
-    bool shared = false;
-    const int rc = guarded(h, [&] { shared = h->fused_batch->update_vectors(q, l, u); });
-    if (rc != QPS_OK) return rc;
-    return shared ? QPS_OK : fail_with(h, QPS_ERR_BAD_ARGUMENT, "not a shared-matrix batch handle");
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "not a shared-matrix batch handle");
+    return guarded(h, [&] { fam->update_vectors(q, l, u); });
 }
 
 QPS_API int32_t qps_set_shared_rho_scale(qps_handle hh, const double* scale) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     const char* other = "qps_set_shared_rho_scale: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) take a per-row rho scale";
-    if (!h->fused_batch || !h->fused_batch->takes_rho_scale()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
     for (int64_t i = 0; scale && i < h->m; ++i)
         if (!(scale[i] > 0) || !std::isfinite(scale[i])) {
             char b[128]; snprintf(b, sizeof b, "rho scale: entry %lld is not a finite positive number", (long long)i);
             return fail_with(h, QPS_ERR_BAD_ARGUMENT, b);
         }
-    return guarded(h, [&] { h->fused_batch->set_rho_scale(scale); });
+    return guarded(h, [&] { fam->set_rho_scale(scale); });
 }
 
 QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
@@ -1934,8 +1215,9 @@ QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     if (mode != 0 && mode != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_adaptive_rho: mode must be 0 (fixed rho) or 1 (family-wide adaptive rho)");
     const char* other = "qps_set_shared_adaptive_rho: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) run the family-wide rho rule";
-    if (!h->fused_batch || !h->fused_batch->takes_family_rho()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
-    h->fused_batch->family_rho = mode;
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    fam->family_rho = mode;
     return QPS_OK;
 }
 
@@ -1944,8 +1226,9 @@ QPS_API int32_t qps_set_shared_warm_start(qps_handle hh, int32_t mode) {
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     if (mode < 0 || mode > 2) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_warm_start: mode must be 0 (z = y = 0), 1 (the stored z and y) or 2 (z = A x, the stored y)");
     const char* other = "qps_set_shared_warm_start: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) keep z and y between solves";
-    if (!h->fused_batch || !h->fused_batch->takes_warm_start()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
-    h->fused_batch->warm_start = mode;
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    fam->warm_start = mode;
     return QPS_OK;
 }
 
@@ -1953,11 +1236,12 @@ QPS_API int32_t qps_set_shared_dual(qps_handle hh, const double* z, const double
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     const char* other = "qps_set_shared_dual: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) keep z and y between solves";
-    if (!h->fused_batch || !h->fused_batch->takes_warm_start()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
     const int64_t c = h->fused_batch->count;
     if (z && !all_finite(z, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_dual: z contains NaN/Inf (the handle keeps its state)");
     if (y && !all_finite(y, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_dual: y contains NaN/Inf (the handle keeps its state)");
-    return guarded(h, [&] { h->fused_batch->set_dual(z, y); });
+    return guarded(h, [&] { fam->set_dual(z, y); });
 }
 
 QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {
@@ -1965,18 +1249,19 @@ QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     if (passes < 0 || passes > 50) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_equilibration: passes must be in 0..50 (0 switches the scaling off)");
     const char* other = "qps_set_shared_equilibration: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) are equilibrated";
-    if (!h->fused_batch || !h->fused_batch->takes_equilibration()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
-    return guarded(h, [&] { h->fused_batch->set_equilibration(passes); });
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    return guarded(h, [&] { fam->set_equilibration(passes); });
 }
 
 QPS_API int32_t qps_get_shared_equilibration(qps_handle hh, double* d_out, double* e_out) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
     const char* other = "qps_get_shared_equilibration: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) are equilibrated";
-    if (!h->fused_batch || !h->fused_batch->takes_equilibration()) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
-    const BatchSolverBase& s = *h->fused_batch;
-    for (int64_t j = 0; d_out && j < h->n; ++j) d_out[j] = s.eq_kd.empty() ? 1.0 : std::ldexp(1.0, s.eq_kd[j]);
-    for (int64_t i = 0; e_out && i < h->m; ++i) e_out[i] = s.eq_ke.empty() ? 1.0 : std::ldexp(1.0, s.eq_ke[i]);
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    for (int64_t j = 0; d_out && j < h->n; ++j) d_out[j] = fam->eq_kd.empty() ? 1.0 : std::ldexp(1.0, fam->eq_kd[j]);
+    for (int64_t i = 0; e_out && i < h->m; ++i) e_out[i] = fam->eq_ke.empty() ? 1.0 : std::ldexp(1.0, fam->eq_ke[i]);
     return QPS_OK;
 }
 

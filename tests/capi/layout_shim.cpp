@@ -1,5 +1,5 @@
-// layout_shim.cpp -- TEST INFRASTRUCTURE: a C ABI over the host-only code of the product (spmv_layout.cpp, ldl_symbolic.cpp) so that CPU tests can
-// expand every SpMV layout back into a matrix-vector product and run the symbolic analysis without a GPU.  Built with g++ by
+// layout_shim.cpp -- TEST INFRASTRUCTURE: a C ABI over the host-only code of the product (spmv_layout.cpp, ldl_symbolic.cpp, the header-only rules) so that CPU tests can
+// expand every SpMV layout back into a matrix-vector product, run the symbolic analysis and call the host rules of the shared-matrix batches without a GPU.  Built with g++ by
 // `make -C quadraticprogramsolver_amd/csrc host-test` (SAN=1: -fsanitize=address,undefined) into libqps_host_test[_san].so; never part of libqps_hip.so.
 #include <cstdint>
 #include <cstring>
@@ -9,6 +9,7 @@
 
 #include "../../quadraticprogramsolver_amd/csrc/batch_schedule.h"
 #include "../../quadraticprogramsolver_amd/csrc/ldl_symbolic.h"
+#include "../../quadraticprogramsolver_amd/csrc/shared_family_rules.h"
 #include "../../quadraticprogramsolver_amd/csrc/spmv_layout.h"
 #include "../../quadraticprogramsolver_amd/csrc/tile_order.h"
 
@@ -131,6 +132,15 @@ SHIM_API int lt_ldl_analyze(int n, int m, const int64_t* Pcp, const int64_t* Pri
         if (report) { report[0] = s.N; report[1] = s.Ns; report[2] = s.Nt; report[3] = (int64_t)s.level_ptr.size() - 1; report[4] = s.levels_total; report[5] = s.nnzK; report[6] = s.nnzL_exact; report[7] = s.nnzL; }
         return 0;
     } catch (const std::exception&) { return -1; }
+}
+// The two host rules of the shared-matrix batches (shared_family_rules.h) as the solvers call them.  res: 8 doubles per column ([0..3] the four norms), active: one
+// word per column; step: the exponent step of one equilibration pass for the norm v, *clamp (may be NULL) the bound of the exponents.
+SHIM_API double lt_family_rho_proposal(const double* res, const int* active, int count, double rho, double rhorho) {
+    return family_rho_proposal(res, std::vector<int>(active, active + count), count, rho, rhorho);
+}
+SHIM_API int lt_equil_step(double v, int* clamp) {
+    if (clamp) *clamp = EQUIL_CLAMP;
+    return equil_step(v);
 }
 // The id -> tile maps of tile_order.h walked over a whole launch: tiles[(bi * nt + bj)] counts how often tile (bi, bj) was dealt.  kind 0: k_gemm's lower tiles of an
 // nt x nt grid (returns the number of ids of the launch, ids_per_xcd_span[x] = number of distinct tile ROWS + COLUMNS XCD x touches in its first 64 tiles);

@@ -2,7 +2,8 @@
 header, library, ctypes and Julia; a NULL handle and a bad pass count are refused without a device; and every case the GPU tests of
 tests/test_gpu_equilibration.py use passes its guard in the numpy restatement of tests/equilibration_cases.py -- the reduced and the KKT form take the same
 decisions and agree at the fixed K to a tenth of the device bound, no decision of the family-wide rho rule sits on a rounding edge, and the families do what the
-tests say they do (the scrambled family needs the scaling, the spread-4 family reaches both clamps)."""
+tests say they do (the scrambled family needs the scaling, the spread-4 family reaches both clamps).  The step of one pass as the library computes it
+(equil_step of csrc/shared_family_rules.h, through the host-test shim) is the restated integer rule."""
 import ctypes as C
 import os
 import re
@@ -57,6 +58,22 @@ def test_the_rule_on_a_matrix_worked_by_hand():
     kd2, ke2 = ec.ruiz_pow2(P, A, 2)
     assert kd2.tolist() == [-2, 3] and ke2.tolist() == [-1, 0]
     assert ec.ruiz_pow2(P, A, 0)[0].tolist() == [0, 0]
+
+
+STEP_INPUTS = [0.0, -3.0, 1.0, 0.5, 2.0, 4.0, 3.0, 2.0 ** -1021, 5e-324, 1e308]
+#   v = f 2^e, f in [0.5, 1):  -   -    e=1  e=0  e=2  e=3  e=2  e=-1020      e=-1073 e=1024
+STEP_BY_HAND = [0, 0, 0, 0, -1, -1, -1, 510, 537, -512]
+
+
+def test_the_library_step_is_the_restated_integer_rule():
+    """-floor(e / 2) with floor towards minus infinity (e = 1 gives 0, e = -1073 gives +537), 0 for a norm that is not positive; the clamp is the restatement's."""
+    from host_shim import rules
+    clamp = C.c_int(0)
+    got = [rules().lt_equil_step(v, C.byref(clamp)) for v in STEP_INPUTS]
+    want = [int(k) for k in ec._step(np.array(STEP_INPUTS))]
+    print("v", STEP_INPUTS, "library", got, "restatement", want)
+    assert got == want == STEP_BY_HAND
+    assert clamp.value == ec.K_CLAMP
 
 
 def test_fp32_handles_scale_the_rounded_matrices():

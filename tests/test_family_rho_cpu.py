@@ -1,8 +1,10 @@
 """CPU-only checks of the family-wide adaptive rho of the shared-matrix batches (qps_set_shared_adaptive_rho): the symbol is declared, exported and bound in
 header, library, ctypes and Julia; a NULL handle and a bad mode are refused without a device; at count = 1 the numpy restatement of tests/family_rho_cases.py --
 the reference of the GPU tests -- is the reference loop with adptΡ = true; and every row of the case table passes its guard: both linear-system forms take the
-same decisions, no decision of the rule sits on a rounding edge, and the two forms agree in the switched rho to what the GPU bound of the row allows."""
+same decisions, no decision of the rule sits on a rounding edge, and the two forms agree in the switched rho to what the GPU bound of the row allows.  The
+proposal the library itself computes (family_rho_proposal of csrc/shared_family_rules.h, through the host-test shim) equals that restatement to the last bit."""
 import ctypes as C
+import math
 import os
 import re
 
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 from family_rho_cases import CASES, EPS, NUM_ITR_CONV, RHO, FamilyRestatement, case_run, family_proposal
+from host_shim import rules
 from oracle.qps_oracle_np import RedChol, RedCholInit, SolveQuadraticProgramRefLoop
 from shared_batch_cases import shared_family
 
@@ -51,6 +54,44 @@ def test_proposal_picks_the_worst_running_columns():
     assert np.isnan(family_proposal(norms, [3], 0.1, 7.0))                           # all NaN: a NaN proposal, which never passes the switch test
     assert family_proposal(norms, [], 0.1, 7.0) == 7.0
     assert family_proposal({0: (1.0, 1e-20, 1.0, 1.0)}, [0], 1.0, 1.0) == 1e6 and family_proposal({0: (1e-20, 1.0, 1.0, 1.0)}, [0], 1.0, 1.0) == 1e-3
+
+
+NAN = float("nan")
+# (name, norms per column as (normResPrim, normResDual, maxNormPrim, maxNormDual), running columns, rho, rhorho)
+PROPOSAL_INPUTS = [
+    ("three columns, the norms from two of them", [(1.0, 1.0, 10.0, 10.0), (3.0, 0.5, 10.0, 10.0), (0.7, 2.0, 10.0, 5.0)], [0, 1, 2], 0.1, 7.0),
+    ("a tie: the lowest index wins", [(1.0, 1.0, 10.0, 10.0), (4.0, 0.5, 10.0, 10.0), (4.0, 2.0, 10.0, 5.0), (8.0, 3.0, 20.0, 7.5)], [0, 1, 2, 3], 0.1, 7.0),
+    ("a NaN quotient loses to a number, first or last", [(NAN, NAN, 1.0, 1.0), (0.3, 0.2, 7.0, 3.0), (NAN, 0.1, 1.0, 3.0)], [0, 1, 2], 0.25, 7.0),
+    ("all quotients NaN", [(NAN, NAN, 1.0, 1.0), (NAN, NAN, 2.0, 2.0)], [0, 1], 0.1, 7.0),
+    ("one running column of three", [(1.0, 1.0, 10.0, 10.0), (0.3, 0.011, 7.0, 3.0), (9.0, 9.0, 1.0, 1.0)], [1], 0.1, 7.0),
+    ("no running column: rhorho comes back", [(1.0, 1.0, 10.0, 10.0), (0.3, 0.011, 7.0, 3.0)], [], 0.1, 7.0),
+    ("clamped at 1e6", [(1.0, 1e-20, 1.0, 1.0)], [0], 1.0, 1.0),
+    ("clamped at 1e-3", [(1e-20, 1.0, 1.0, 1.0)], [0], 1.0, 1.0),
+    ("a zero dual residual: the denominator is 0", [(0.5, 0.0, 2.0, 3.0), (0.25, 0.0, 2.0, 3.0)], [0, 1], 0.1, 7.0),
+    ("zero over zero", [(0.0, 0.0, 2.0, 3.0)], [0], 0.1, 7.0),
+    ("a zero maximum norm: an infinite quotient wins", [(0.5, 0.5, 0.0, 3.0), (0.25, 0.75, 2.0, 3.0)], [0, 1], 0.1, 7.0),
+]
+
+
+@pytest.mark.parametrize("name,norms,running,rho,rhorho", PROPOSAL_INPUTS, ids=[c[0] for c in PROPOSAL_INPUTS])
+def test_the_library_proposal_is_the_restatement_to_the_last_bit(name, norms, running, rho, rhorho):
+    """family_rho_proposal as the solvers call it -- 8 doubles per column, one active word per column -- against family_proposal: the same double, or NaN on both
+    sides (a NaN carries no value to compare).  The expected values of the plain cases are written out as well, so the two cannot be wrong together there."""
+    count = len(norms)
+    res = np.full(8 * count, -777.0)                             # slots 4..7 of a column are not the rule's business
+    for b, four in enumerate(norms):
+        res[8 * b:8 * b + 4] = four
+    act = np.zeros(count, dtype=np.int32); act[running] = 1
+    got = rules().lt_family_rho_proposal(res.ctypes.data_as(C.POINTER(C.c_double)), act.ctypes.data_as(C.POINTER(C.c_int)), count, rho, rhorho)
+    want = family_proposal(dict(enumerate(norms)), running, rho, rhorho)
+    print(f"{name}: library {got!r}, restatement {want!r}")
+    assert (math.isnan(got) and math.isnan(want)) or got == want
+    by_hand = {"three columns, the norms from two of them": 0.1 * math.sqrt((3.0 * 5.0) / (2.0 * 10.0)), "a tie: the lowest index wins": 0.1,
+               "no running column: rhorho comes back": 7.0, "clamped at 1e6": 1e6, "clamped at 1e-3": 1e-3, "a zero dual residual: the denominator is 0": 1e6}
+    if name in by_hand:
+        assert got == by_hand[name]
+    if name in ("all quotients NaN", "zero over zero"):
+        assert math.isnan(got)
 
 
 @pytest.mark.parametrize("b", [0, 1, 3])

@@ -9,6 +9,9 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from shared_batch_cases import shared_family
+from sparse_shared_cases import lasso_path
+
 pytestmark = pytest.mark.gpu
 
 MiB = 1 << 20
@@ -44,7 +47,7 @@ def _proxqp_problem(q, n, me, mi, stream):
 
 def _cycles(q):
     """One create -> solve -> destroy cycle per handle kind; every kind allocates differently (dense factor + inverse, batch slabs, CSR pairs + sliced layouts,
-    explicit reduced matrix, sparse L D L' levels, ProxQP KKT)."""
+    explicit reduced matrix, sparse L D L' levels, ProxQP KKT, the shared-matrix batches with every option that allocates)."""
     dense = q.GenerateDenseBenchmarkQP(700, 1300, stream=3, feasible=True)
     wide = q.GenerateDenseBenchmarkQP(2100, 300, stream=4, feasible=True)
     batch = [q.GenerateDenseBenchmarkQP(200, 400, stream=20 + b, feasible=True) for b in range(6)]
@@ -53,6 +56,9 @@ def _cycles(q):
     iso = q.GenerateRandomQP(q.ProblemClass.isotonicRegression, 20, rng=q.make_rng(9, 10))
     pq = _proxqp_problem(q, 150, 20, 120, 1)
     pqs = tuple(sp.csc_matrix(a) if a.ndim == 2 else a for a in pq)
+    # 20 columns are 32 panel columns: one state panel is 32 x 2048 (2448 sparse) doubles = 512 (612) KiB, so one panel leaked per cycle shows as >= 6 MiB
+    dense_family = shared_family(1024, 2048, 20)
+    sparse_family = lasso_path(24, 20)                          # n = m = 2448
 
     def run_dense(problem, dtype, **kw):
         P, qq, A, l, u = problem
@@ -82,6 +88,17 @@ def _cycles(q):
             z, y = prob.dual()
             prob.polish(x, y)
 
+    def run_shared(cls, family):
+        P, A, Q, L, U = family
+        with cls(P, A, Q, L, U) as fam:
+            fam.set_rho_scale(q.equality_rho_scale(L, U))
+            fam.set_equilibration(10)
+            fam.set_adaptive_rho(True)
+            fam.set_warm_start("state")
+            for _ in range(2):
+                fam.solve(numIterations=60, ϵAbs=0.0, ϵRel=0.0, ρ=0.1, numItrConv=25)
+            fam.dual()
+
     return {
         "dense f64": lambda: run_dense(dense, "f64"),
         "dense f32": lambda: run_dense(dense, "f32"),
@@ -94,6 +111,8 @@ def _cycles(q):
         "proxqp dense": lambda: run_proxqp(pq),
         "proxqp sparse": lambda: run_proxqp(pqs),
         "polish": run_polish,
+        "shared dense f64, all options": lambda: run_shared(q.QuadraticProgramSharedBatch, dense_family),
+        "shared sparse f64, all options": lambda: run_shared(q.QuadraticProgramSparseSharedBatch, sparse_family),
     }
 
 
