@@ -47,7 +47,11 @@ typedef enum {
 } qps_status;
 
 /* SolveQuadraticProgram.jl:12  @enum ConvergenceFlag convNumItr = 1 convAdmm convPrimDual */
-typedef enum { QPS_CONV_NUM_ITR = 1, QPS_CONV_ADMM = 2, QPS_CONV_PRIM_DUAL = 3 } qps_conv_flag;
+typedef enum {
+    QPS_CONV_NUM_ITR = 1, QPS_CONV_ADMM = 2, QPS_CONV_PRIM_DUAL = 3,
+    /* additive, issued only by a shared-matrix batch handle with qps_set_shared_infeasibility on */
+    QPS_CONV_PRIMAL_INFEASIBLE = 4, QPS_CONV_DUAL_INFEASIBLE = 5
+} qps_conv_flag;
 
 /* arithmetic type of the device-resident loop */
 typedef enum { QPS_F64 = 0, QPS_F32 = 1 } qps_dtype;
@@ -307,6 +311,44 @@ int32_t qps_get_shared_equilibration(qps_handle h, double *d_out /* [n] or NULL 
  * Out of scope: stand-alone handles, qps_create_dense_batch, ProxQP handles (qps_proxqp_set_state serves them) and polishing. */
 int32_t qps_set_shared_warm_start(qps_handle h, int32_t mode /* 0 z = y = 0 (default), 1 the stored z and y, 2 z = A x and the stored y */);
 int32_t qps_set_shared_dual(qps_handle h, const double *z, const double *y);   /* [count][m] each; NULL keeps that array */
+
+/* Per-column infeasibility certificates of a shared-matrix batch handle (dense or sparse; section 3.4 of the OSQP paper), opt-in.  Without it a column that has no
+ * solution can only end with flag 1 at numIterations: the whole batch pays its launch chain to the end, under qps_set_shared_adaptive_rho it steers the family rho
+ * for everyone, and the caller cannot tell "needs more iterations" from "has no solution".  With it such a column stops at a check with a flag of its own and a
+ * certificate.  Nothing in the iteration changes; all of the work happens at the checks.
+ * The rule, per column, at a check (every numItrConv iterations), in the caller's units.  A column is examined only if it is still running and CheckConvergence
+ * leaves its flag at 1 at this check: flags 2 and 3 are decided as before and win.  dx = x - xp and dy = y - y_prev, y_prev being y before this iteration's row
+ * update; both differences are formed in the handle's type.
+ *   Primal infeasible (QPS_CONV_PRIMAL_INFEASIBLE = 4): dyh = dy projected onto the polar of the recession cone of [l, u] -- dyh_i = 0 if l_i = -Inf and u_i = +Inf,
+ *   min(dy_i, 0) if only u_i = +Inf, max(dy_i, 0) if only l_i = -Inf, dy_i otherwise.  With N = ||dyh||_inf and S = sum_{dyh_i > 0} u_i dyh_i + sum_{dyh_i < 0}
+ *   l_i dyh_i (entries with dyh_i = 0 are skipped: 0 * Inf never arises), the column is primal infeasible iff
+ *       N > epsPrimInf   and   S < -epsPrimInf N   and   ||A'dyh||_inf < epsPrimInf N.
+ *   Dual infeasible (QPS_CONV_DUAL_INFEASIBLE = 5), tested only if the primal test failed: with M = ||dx||_inf, iff
+ *       M > epsDualInf   and   q'dx < -epsDualInf M   and   ||P dx||_inf < epsDualInf M   and for every row i:
+ *       u_i finite implies (A dx)_i < epsDualInf M,   l_i finite implies (A dx)_i > -epsDualInf M.
+ *   Every comparison with a NaN operand is false: no certificate.  The norms are inf-norms; the two sums are formed and added in double whatever the handle's type,
+ *   in an order that depends on n and m only -- a column of a batch stays bit-identical to the same data in a batch of one, certificate included.
+ * A column that gets flag 4 or 5 stops like any other: it is frozen by the active mask, qps_info.iterations is this check's iteration, x, z, y (qps_get_dual) are
+ * the iterates of that iteration, resPrim / resDual those of that check, and it leaves the "columns still running" of the family-wide rho rule.
+ * epsPrimInf = epsDualInf = 0 (the default) turns the option off: the handle behaves exactly as without it, bit for bit.  A positive finite value turns that test
+ * on; one of the two may be 0 to leave that test off.  OSQP's default for each is 1e-4.  The setting is a property of the handle and persists across solves; it does
+ * not touch the factorisation, the stored z and y, or reuseFactor.  With it on and every column feasible the results equal those with it off, bit for bit.
+ * Interactions.  Rho scale: it does not enter the rule.  Family-wide rho: a switch happens at the top of an iteration, so dy spans one iteration at one rho.
+ * Equilibration: the rule sees the caller's units, as the convergence check does -- dy = E dy~, dx = D dx~, A'dyh = D^-1 A~'dyh~, P dx = D^-1 P~ dx~, A dx = E^-1 A~
+ * dx~, all moves exact powers of two; the two sums do not change under the scaling.  Warm-start modes 1 and 2: unchanged (xp and y_prev are defined at the first check).
+ * Cost: per check one copy of the y panels, two small launches and the check's three matrix products once more, on the differences; the flags travel in the
+ * read-back the check makes anyway (still one device-to-host copy and one stream synchronisation per check).  While the option is on the handle holds three more
+ * panel arrays ([count][m] twice, [count][n] once) and a small reduction buffer; they are released when it is turned off.
+ * fp32 handles: dy is a difference of fp32 iterates, so its absolute error is half an ulp of y, and y of an infeasible column grows with every iteration; ||A'dyh|| /
+ * ||dyh|| then stops falling around 1e-4 .. 1e-3 (measured: 2e-4 at n = 96, m = 160).  Give an fp32 handle 1e-3; at 1e-4 such a column may never be flagged.
+ * qps_get_shared_certificate: row b of dy ([count][m]) is dyh of column b if its last qps_solve_batch ended with flag 4, else zeros; row b of dx ([count][n]) is dx
+ * if it ended with flag 5, else zeros -- both of the column's own stopping check, in the caller's units, unnormalised.  Either pointer may be NULL.  Zeros before any
+ * solve, after a solve that returned an error, after the option was turned off and after a change of the equilibration.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, or a negative, NaN or Inf value (before a device is needed; the handle keeps its state).  QPS_ERR_UNSUPPORTED
+ * (qps_last_error names the reason): any handle that is not a shared-matrix batch.
+ * Out of scope: stand-alone handles, qps_create_dense_batch, qps_solve_batch_multi, ProxQP handles and the CG plugins. */
+int32_t qps_set_shared_infeasibility(qps_handle h, double epsPrimInf, double epsDualInf);   /* 0, 0 = off (default); OSQP: 1e-4, 1e-4 */
+int32_t qps_get_shared_certificate(qps_handle h, double *dy /* [count][m] or NULL */, double *dx /* [count][n] or NULL */);
 
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix

@@ -463,7 +463,29 @@ function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIteration
     buf = Vector{UInt8}(undef, count * sizeof(QpsInfo))
     GC.@preserve mX buf _check(ccall((:qps_solve_batch, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
                                      h, mX, Ref(prm), buf), h)
-    return [ConvergenceFlag(unsafe_load(Ptr{Int32}(pointer(buf) + (b - 1) * sizeof(QpsInfo)))) for b in 1:count]
+    return [_shared_conv_flag(unsafe_load(Ptr{Int32}(pointer(buf) + (b - 1) * sizeof(QpsInfo)))) for b in 1:count]
+end
+
+# Per-column infeasibility certificates (qps_set_shared_infeasibility; OSQP section 3.4), opt-in.  The reference's ConvergenceFlag (SolveQuadraticProgram.jl:12) ends at
+# convPrimDual = 3; the two flags only a shared-matrix batch with this option on can return are an enum of their own (QPS_CONV_PRIMAL_INFEASIBLE, QPS_CONV_DUAL_INFEASIBLE).
+@enum InfeasibilityFlag convPrimInfeasible = 4 convDualInfeasible = 5
+_shared_conv_flag(v::Integer) = v <= 3 ? ConvergenceFlag(v) : InfeasibilityFlag(v)
+
+# ϵPrimInf, ϵDualInf: finite and >= 0 (OSQP: 1e-4 each); nothing / false / 0 leaves that test off, both off is the default.  The setting stays with the handle.
+function SharedBatchSetInfeasibility!(sb::SharedBatchHip; ϵPrimInf::Union{Nothing, Bool, Real} = 1e-4, ϵDualInf::Union{Nothing, Bool, Real} = 1e-4)
+    h = sb.h
+    e(v) = (v === nothing || v === false) ? 0.0 : Float64(v)
+    _check(ccall((:qps_set_shared_infeasibility, LIBQPS), Int32, (Ptr{Cvoid}, Float64, Float64), h, e(ϵPrimInf), e(ϵDualInf)), h)
+    return nothing
+end
+
+# (mDY [m x count], mDX [n x count]) of the last SharedBatchSolve!: column b of mDY is the projected δy if that QP ended with convPrimInfeasible, column b of mDX its δx
+# if it ended with convDualInfeasible, zeros otherwise (the caller's units, unnormalised)
+function SharedBatchCertificate(sb::SharedBatchHip)
+    h = sb.h
+    mDY = zeros(sb.m, sb.count); mDX = zeros(sb.n, sb.count)
+    GC.@preserve mDY mDX _check(ccall((:qps_get_shared_certificate, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h, mDY, mDX), h)
+    return mDY, mDX
 end
 
 SharedBatchDestroy(sb::SharedBatchHip) = ccall((:qps_destroy, LIBQPS), Int32, (Ptr{Cvoid},), sb.h)

@@ -400,6 +400,131 @@ __global__ void k_shared_decide(int cols, const unsigned long long* __restrict__
     res[4] = rho; res[5] = (double)flag; res[6] = nv[7]; res[7] = nv[8];
 }
 
+// ---- infeasibility certificates (qps_set_shared_infeasibility; OSQP 3.4): three launches at a check, none in the iteration -----------------------------------
+// dx = x - xp (n rows) and dyh = the projection of y - yp onto the polar of the recession cone of [l, u] (m rows; yp = y before this iteration's row update), for
+// the columns of the active mask: a column that stopped keeps the differences of its own stopping check, padding rows and columns keep their zeros.  Differences
+// are formed in T, as the check forms its own.  The projection keeps a NaN (d > 0 ? 0 : d), so a NaN difference reaches the norm and no certificate is issued.
+// With equilibration the panels hold the scaled iterates and so do dx and dyh: a positive row scale changes neither a sign nor which bound is infinite.
+template <typename T>
+__global__ __launch_bounds__(256) void k_shared_deltas(int n, int m, int NP, int MP, const T* __restrict__ x, const T* __restrict__ xp, const T* __restrict__ y,
+                                                       const T* __restrict__ yp, const T* __restrict__ l, const T* __restrict__ u, const int* __restrict__ active,
+                                                       T* __restrict__ dx, T* __restrict__ dyh) {
+    const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    if (!active[P * 16 + col]) return;
+    const int64_t on = (int64_t)P * NP * 16 + col, om = (int64_t)P * MP * 16 + col;
+    for (int r = blockIdx.x * 16 + rl; r < max(n, m); r += gridDim.x * 16) {
+        if (r < m) {
+            const int64_t i = om + (int64_t)r * 16;
+            const T d = y[i] - yp[i];
+            const bool lo_inf = l[i] == -(T)INFINITY, hi_inf = u[i] == (T)INFINITY;
+            dyh[i] = (lo_inf && hi_inf) ? T(0) : hi_inf ? (d > T(0) ? T(0) : d) : lo_inf ? (d < T(0) ? T(0) : d) : d;
+        }
+        if (r < n) {
+            const int64_t i = on + (int64_t)r * 16;
+            dx[i] = x[i] - xp[i];
+        }
+    }
+}
+
+// The seven figures of the two tests, per column, over the rows of one workgroup: part[(column * gridDim.x + blockIdx.x) * 8 + k], k =
+//   0 ||dyh||  1 ||A'dyh||  2 S = sum_{dyh_i > 0} u_i dyh_i + sum_{dyh_i < 0} l_i dyh_i  3 ||dx||  4 ||P dx||  5 q'dx
+//   6 the largest violation of the sign test on A dx: max(0, (A dx)_i over rows with a finite u_i, -(A dx)_i over rows with a finite l_i)
+// all inf-norms, in the caller's units (EQ: E on dyh, D on dx, D^-1 on A'dyh and P dx, E^-1 on A dx -- exact powers of two, in double; the two sums are invariant
+// under the scaling and are taken on the stored panels).  Norms travel as the bit patterns of non-negative doubles, so a NaN wins every maximum (k_shared_norms).
+// The sums: every term is formed and added in double; a thread adds its rows in row order, the 16 threads of a column meet through two shuffles and the waves
+// through LDS in wave order, and k_shared_cert_decide adds the workgroups in index order -- an order fixed by n, m and the launch geometry (shared_cert_blocks:
+// n and m only), never by `count` or the column's position.  No atomics, no scratch.  Entries with dyh_i = 0 add nothing, so 0 * Inf never arises; dyh_i > 0
+// implies a finite u_i and dyh_i < 0 a finite l_i by the projection.
+template <typename T, bool EQ>
+__global__ __launch_bounds__(256) void k_shared_cert_partial(int n, int m, int NP, int MP, const T* __restrict__ dx, const T* __restrict__ dyh,
+                                                             const T* __restrict__ Adx, const T* __restrict__ Pdx, const T* __restrict__ Atdy,
+                                                             const T* __restrict__ q, const T* __restrict__ l, const T* __restrict__ u,
+                                                             const int* __restrict__ active, const int* __restrict__ kd, const int* __restrict__ ke,
+                                                             double* __restrict__ part) {
+    __shared__ double red[4][16][8];
+    const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4, wv = threadIdx.x >> 6;
+    const bool act = active[P * 16 + col] != 0;
+    const int64_t on = (int64_t)P * NP * 16 + col, om = (int64_t)P * MP * 16 + col;
+    unsigned long long v[5] = {0ull, 0ull, 0ull, 0ull, 0ull};   // ||dyh||, ||A'dyh||, ||dx||, ||P dx||, violation
+    double S = 0.0, qd = 0.0;
+    for (int r = blockIdx.x * 16 + rl; act && r < max(n, m); r += gridDim.x * 16) {
+        if (r < m) {
+            const int64_t i = om + (int64_t)r * 16;
+            const T dv = dyh[i], lo = l[i], hi = u[i];
+            const int s = EQ ? ke[r] : 0;
+            v[0] = sh_umax(v[0], sh_absbits(EQ ? ldexp((double)dv, s) : (double)dv));
+            if (dv > T(0)) S += (double)hi * (double)dv;
+            else if (dv < T(0)) S += (double)lo * (double)dv;
+            const double a = EQ ? ldexp((double)Adx[i], -s) : (double)Adx[i];
+            if (hi != (T)INFINITY && !(a <= 0.0)) v[4] = sh_umax(v[4], sh_absbits(a));      // (a NaN counts as a violation)
+            if (lo != -(T)INFINITY && !(a >= 0.0)) v[4] = sh_umax(v[4], sh_absbits(a));
+        }
+        if (r < n) {
+            const int64_t i = on + (int64_t)r * 16;
+            const T d = dx[i];
+            const int s = EQ ? kd[r] : 0;
+            v[2] = sh_umax(v[2], sh_absbits(EQ ? ldexp((double)d, s) : (double)d));
+            v[3] = sh_umax(v[3], sh_absbits(EQ ? ldexp((double)Pdx[i], -s) : (double)Pdx[i]));
+            v[1] = sh_umax(v[1], sh_absbits(EQ ? ldexp((double)Atdy[i], -s) : (double)Atdy[i]));
+            qd += (double)q[i] * (double)d;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        v[k] = sh_umax(v[k], __shfl_xor(v[k], 16));
+        v[k] = sh_umax(v[k], __shfl_xor(v[k], 32));
+    }
+    S += __shfl_xor(S, 16); S += __shfl_xor(S, 32);       // a + b is the same double on both lanes of a pair
+    qd += __shfl_xor(qd, 16); qd += __shfl_xor(qd, 32);
+    if ((threadIdx.x & 63) < 16) {
+        double* o = red[wv][col];
+        o[0] = __longlong_as_double((long long)v[0]); o[1] = __longlong_as_double((long long)v[1]); o[2] = S;
+        o[3] = __longlong_as_double((long long)v[2]); o[4] = __longlong_as_double((long long)v[3]); o[5] = qd;
+        o[6] = __longlong_as_double((long long)v[4]); o[7] = 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16 && act) {
+        double o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = red[0][col][k];
+        for (int ww = 1; ww < 4; ++ww)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const double t = red[ww][col][k];
+                if (k == 2 || k == 5 || k == 7) o[k] += t;
+                else o[k] = __longlong_as_double((long long)sh_umax((unsigned long long)__double_as_longlong(o[k]), (unsigned long long)__double_as_longlong(t)));
+            }
+        double* dst = part + ((int64_t)(P * 16 + col) * gridDim.x + blockIdx.x) * 8;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dst[k] = o[k];
+    }
+}
+
+// The two tests for every column that is still running and that k_shared_decide left at flag 1 (flags 2 and 3 win): res[5] becomes 4 (primal infeasible) or 5
+// (dual infeasible, tested only when the primal test failed), so the flags travel in the read-back the check makes anyway.  epsP / epsD = 0: that test is off.
+// Every comparison with a NaN operand is false: no certificate.
+__global__ void k_shared_cert_decide(int cols, int nblk, const double* __restrict__ part, double* __restrict__ res, const int* __restrict__ active, double epsP,
+                                     double epsD) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= cols || !active[b]) return;
+    res += (int64_t)b * 8;
+    if (res[5] != 1.0) return;
+    part += (int64_t)b * nblk * 8;
+    double o[8];
+    for (int k = 0; k < 8; ++k) o[k] = part[k];
+    for (int j = 1; j < nblk; ++j)
+        for (int k = 0; k < 8; ++k) {
+            const double t = part[j * 8 + k];
+            if (k == 2 || k == 5 || k == 7) o[k] += t;
+            else o[k] = __longlong_as_double((long long)sh_umax((unsigned long long)__double_as_longlong(o[k]), (unsigned long long)__double_as_longlong(t)));
+        }
+    const double N = o[0], At = o[1], S = o[2], M = o[3], Pn = o[4], qd = o[5], V = o[6];
+    const bool prim = (epsP > 0.0) && (N > epsP) && (S < -epsP * N) && (At < epsP * N);
+    const bool dual = !prim && (epsD > 0.0) && (M > epsD) && (qd < -epsD * M) && (Pn < epsD * M) && (V < epsD * M);
+    if (prim) res[5] = 4.0;
+    else if (dual) res[5] = 5.0;
+}
+
 // host layout [count][len] doubles <-> panels [panel][rowsP][16] of T
 template <typename T>
 __global__ void k_to_panels(const double* __restrict__ src, int count, int len, int rowsP, T* __restrict__ dst) {
@@ -509,6 +634,25 @@ void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, cons
     hipLaunchKernelGGL(k_shared_decide, dim3((npanel * 16 + 63) / 64), dim3(64), 0, st, npanel * 16, slots, res_dev, active, epsAbs, epsRel, epsAdmm, rho);
 }
 
+// workgroups per panel of the certificate sums: from n and m only, so that the summation order of a column never depends on the batch around it
+int shared_cert_blocks(int n, int m) { return std::max(1, std::min((std::max(n, m) + 255) / 256, 64)); }
+
+template <typename T>
+void shared_deltas(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* x, const T* xp, const T* y, const T* yp, const T* l, const T* u,
+                   const int* active, T* dx, T* dyh) {
+    const int blocks = std::max(1, std::min((std::max(n, m) + 15) / 16, 256));
+    hipLaunchKernelGGL((k_shared_deltas<T>), dim3(blocks, npanel), dim3(256), 0, st, n, m, NP, MP, x, xp, y, yp, l, u, active, dx, dyh);
+}
+template <typename T>
+void shared_certificates(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* dx, const T* dyh, const T* Adx, const T* Pdx, const T* Atdy,
+                         const T* q, const T* l, const T* u, const int* active, const int* kd, const int* ke, double* part, double* res_dev, double epsP,
+                         double epsD) {
+    const int nblk = shared_cert_blocks(n, m);
+    if (kd) hipLaunchKernelGGL((k_shared_cert_partial<T, true>), dim3(nblk, npanel), dim3(256), 0, st, n, m, NP, MP, dx, dyh, Adx, Pdx, Atdy, q, l, u, active, kd, ke, part);
+    else hipLaunchKernelGGL((k_shared_cert_partial<T, false>), dim3(nblk, npanel), dim3(256), 0, st, n, m, NP, MP, dx, dyh, Adx, Pdx, Atdy, q, l, u, active, kd, ke, part);
+    hipLaunchKernelGGL(k_shared_cert_decide, dim3((npanel * 16 + 63) / 64), dim3(64), 0, st, npanel * 16, nblk, part, res_dev, active, epsP, epsD);
+}
+
 template <typename T> void to_panels(hipStream_t st, const double* src, int count, int len, int rowsP, T* dst) {
     const int64_t total = (int64_t)count * len;
     if (total <= 0) return;
@@ -574,6 +718,11 @@ template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int
     template void shared_check<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,     \
                                   const T*, const T*, unsigned long long*, double*, const int*, double, double, double, double,          \
                                   const int*, const int*);                                                                              \
+    template void shared_deltas<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*, const T*,    \
+                                   const int*, T*, T*);                                                                                 \
+    template void shared_certificates<T>(hipStream_t, int, int, int, int, int, const T*, const T*, const T*, const T*, const T*,        \
+                                         const T*, const T*, const T*, const int*, const int*, const int*, double*, double*, double,    \
+                                         double);                                                                                       \
     template void to_panels<T>(hipStream_t, const double*, int, int, int, T*);                                                          \
     template void from_panels<T>(hipStream_t, const T*, int, int, int, double*);                                                        \
     template void transpose_rowmajor<T>(hipStream_t, const T*, int64_t, int, int, T*, int64_t);

@@ -17,6 +17,8 @@ struct SharedFamilyOps {
     virtual void set_rho_scale(const double* scale) = 0;                                  // [m], or NULL
     virtual void set_equilibration(int passes) = 0;                                       // 0..50
     virtual void set_dual(const double* z, const double* y) = 0;                          // [count][m] each, finite; NULL keeps that array
+    virtual void set_infeasibility(double epsPrimInf, double epsDualInf) = 0;             // qps_set_shared_infeasibility: finite, >= 0; both 0 = off
+    virtual void get_certificate(double* dy, double* dx) = 0;                             // [count][m], [count][n]; either may be NULL
 };
 
 struct BatchSolverBase {

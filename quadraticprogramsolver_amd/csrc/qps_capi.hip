@@ -1244,6 +1244,26 @@ QPS_API int32_t qps_set_shared_dual(qps_handle hh, const double* z, const double
     return guarded(h, [&] { fam->set_dual(z, y); });
 }
 
+QPS_API int32_t qps_set_shared_infeasibility(qps_handle hh, double epsPrimInf, double epsDualInf) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (!(epsPrimInf >= 0) || !std::isfinite(epsPrimInf) || !(epsDualInf >= 0) || !std::isfinite(epsDualInf))
+        return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_infeasibility: epsPrimInf and epsDualInf must be finite and >= 0 (0 leaves that test off; the handle keeps its setting)");
+    const char* other = "qps_set_shared_infeasibility: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) issue per-column infeasibility certificates";
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    return guarded(h, [&] { fam->set_infeasibility(epsPrimInf, epsDualInf); });
+}
+
+QPS_API int32_t qps_get_shared_certificate(qps_handle hh, double* dy, double* dx) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    const char* other = "qps_get_shared_certificate: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) issue per-column infeasibility certificates";
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    return guarded(h, [&] { fam->get_certificate(dy, dx); });
+}
+
 QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");

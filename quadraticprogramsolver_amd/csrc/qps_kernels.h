@@ -155,6 +155,19 @@ void shared_check(hipStream_t st, int n, int m, int NP, int MP, int npanel, cons
                   double rho, const int* kd = nullptr, const int* ke = nullptr);
 // kd / ke (both or neither; NP / MP ints): the panels hold iterates scaled by qps_set_shared_equilibration (D = 2^kd on the variables, E = 2^ke on the constraints) and
 // the norms are taken of the unscaled quantities (OSQP 5.1) by a sibling of the norm kernel; without them the launch is the one above, argument for argument.
+// Infeasibility certificates of the shared-matrix batches (qps_set_shared_infeasibility; OSQP 3.4), at a check and only while the option is on.  shared_deltas: for
+// the active columns dx = x - xp (n rows) and dyh = the projection of y - yp onto the polar of the recession cone of [l, u] (m rows); other columns, padding rows
+// and padding columns are left alone.  shared_certificates: Adx = A dx, Pdx = P dx, Atdy = A'dyh come from the check's product launches; per column the norms and
+// the two double sums of the rule are reduced in a fixed order (part: 8 * 16 npanel * shared_cert_blocks(n, m) doubles) and a column that is active and stands at
+// res_dev[8 b + 5] == 1 gets 4 (primal infeasible) or 5 (dual infeasible) there.  epsP / epsD = 0 leaves that test out.  kd / ke as for shared_check.
+int shared_cert_blocks(int n, int m);
+template <typename T>
+void shared_deltas(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* x, const T* xp, const T* y, const T* yp, const T* l, const T* u,
+                   const int* active, T* dx, T* dyh);
+template <typename T>
+void shared_certificates(hipStream_t st, int n, int m, int NP, int MP, int npanel, const T* dx, const T* dyh, const T* Adx, const T* Pdx, const T* Atdy,
+                         const T* q, const T* l, const T* u, const int* active, const int* kd, const int* ke, double* part, double* res_dev, double epsP,
+                         double epsD);
 // Exact power-of-two Ruiz equilibration of the shared-matrix batches (k_shared.hip).  equil_rownorm: out[r] = 2^kr[r] max_c |M[r][c]| 2^kc[c] in double for a
 // row-major rows x K matrix (ld = K, a multiple of 64); lo != NULL: also the smallest non-zero scaled magnitude per row (+Inf: none).  equil_update: k[i] =
 // clamp(k[i] - floor(e / 2), -13, 13) for max(a[i], b[i]) = f 2^e, f in [0.5, 1) (0: k stays; b may be NULL).  scale_two_sided: M[r][c] *= 2^(sign (kr[r] + kc[c]))

@@ -46,6 +46,10 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     // Equilibration (qps_set_shared_equilibration): while it is on, the path's matrices hold D P D and E A D, q, l, u hold D q, E l, E u -- scaled in place by exact
     // powers of two, undone in place when it is cleared -- and kd / ke (rowsN / rowsM ints) are the exponents on the device; the loop kernels run as they are.
     int *kd = nullptr, *ke = nullptr;
+    // Infeasibility certificates (qps_set_shared_infeasibility): while a tolerance is set the handle holds yp (y before the row update of a check iteration), the
+    // projected difference dyh (rowsM) and dxp = x - xp (rowsN) as panels, and the partial sums of the reduction; last_conv: the flags of the last solve.
+    double inf_epsP = 0, inf_epsD = 0; T *yp = nullptr, *dyh = nullptr, *dxp = nullptr; double* cert_part = nullptr; int cat_inf = 0;
+    std::vector<int> last_conv;
     std::vector<int> active;   // the host copy of the mask of the running solve (CP long)
 
     SharedFamilySolver(int dev, int cnt, int64_t n_, int64_t m_, int rowsN_, int rowsM_) {
@@ -105,6 +109,33 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         HIPC(hipStreamSynchronize(st));
     }
     // the vectors the handle keeps between calls, in place: *= 2^(+-k) by the exponents in kd / ke (what both paths' apply_equilibration end with)
+    void set_infeasibility(double epsPrimInf, double epsDualInf) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        if (epsPrimInf > 0 || epsDualInf > 0) {
+            if (!dyh) dyh = mem.dalloc<T>((int64_t)CP * rowsM, st);
+            if (!dxp) dxp = mem.dalloc<T>((int64_t)CP * rowsN, st);
+            if (!cert_part) cert_part = mem.dalloc<double>(8 * (int64_t)CP * shared_cert_blocks((int)n, (int)m), st);
+            if (!yp) yp = mem.dalloc<T>((int64_t)CP * rowsM, st);
+        } else {
+            mem.release(yp); mem.release(dyh); mem.release(dxp); mem.release(cert_part);
+            yp = dyh = dxp = nullptr; cert_part = nullptr;
+        }
+        inf_epsP = epsPrimInf; inf_epsD = epsDualInf;
+    }
+    // row b: dyh (flag 4) or dx (flag 5) of column b's own stopping check in the caller's units (dyh = E dyh~, dx = D dx~ through the check's scratch panels), else zeros
+    void get_certificate(double* dyo, double* dxo) override {
+        HIPC(hipSetDevice(device));
+        auto fetch = [&](double* out, const T* src, const int* k, T* scratch, int64_t len, int rowsP, int flag) {
+            if (!out) return;
+            if (!src || last_conv.empty()) { std::fill(out, out + (size_t)count * (size_t)len, 0.0); return; }
+            if (k) { panel_rowscale<T>(st, src, k, 1, rowsP, npanel, scratch); src = scratch; }
+            get_panels(src, out, len, rowsP);
+            for (int b = 0; b < count; ++b) if (last_conv[b] != flag) std::fill(out + (size_t)b * len, out + (size_t)(b + 1) * len, 0.0);
+        };
+        fetch(dyo, dyh, ke, Ax, m, rowsM, QPS_CONV_PRIMAL_INFEASIBLE);
+        fetch(dxo, dxp, kd, Px, n, rowsN, QPS_CONV_DUAL_INFEASIBLE);
+    }
     void rescale_kept_vectors(int sign) {
         panel_rowscale<T>(st, q, kd, sign, rowsN, npanel, q);
         for (T* v : {l, u, z}) panel_rowscale<T>(st, v, ke, sign, rowsM, npanel, v);
@@ -140,6 +171,12 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         if (kd) panel_rowscale<T>(st, x, kd, -1, rowsN, npanel, x);                                 // warm start in the scaled variables: x~ = D^-1 x
         active.assign(CP, 0);
         for (int b = 0; b < count; ++b) active[b] = 1;
+        const bool certify = inf_epsP > 0 || inf_epsD > 0;                                          // qps_set_shared_infeasibility
+        last_conv.clear();
+        if (certify) {
+            HIPC(hipMemsetAsync(dyh, 0, sizeof(T) * (size_t)CP * rowsM, st));
+            HIPC(hipMemsetAsync(dxp, 0, sizeof(T) * (size_t)CP * rowsN, st));
+        }
         begin_solve(warm_start, rho, sigma, alpha);                                                 // :38-41
         std::vector<int> conv(count, QPS_CONV_NUM_ITR), iters(count, p.numIterations);
         std::vector<double> resP(count, NAN), resD(count, NAN);
@@ -159,13 +196,21 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
                 tref += now_s() - ta;
             }
             const int lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one sample of each category in 50 iterations
+            const bool at_check = ii % p.numItrConv == 0;
+            if (certify && at_check) HIPC(hipMemcpyAsync(yp, y, sizeof(T) * (size_t)CP * rowsM, hipMemcpyDeviceToDevice, st));   // y before this iteration's row update
             iterate(lvl, rho, sigma, alpha);                                                        // LinearSystemSolvers.jl, SolveQuadraticProgram.jl:56-61
-            if (ii % p.numItrConv != 0) continue;                                                   // :63
+            if (!at_check) continue;                                                                // :63
             {
                 ProfScope ps(prof, cat_chk, 2);
                 HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long) * (size_t)CP, st));
-                check_products();                                                                   // mA * vX, mP * vX, mA' * vY
+                check_products(x, y);                                                               // mA * vX, mP * vX, mA' * vY
                 shared_check<T>(st, (int)n, (int)m, rowsN, rowsM, npanel, Ax, Px, Aty, q, x, xp, z, zp, slots, res_dev, d_active, p.epsAbs, p.epsRel, epsAdmm, rho, kd, ke);   // :64
+            }
+            if (certify) {   // OSQP 3.4 on the columns the check left running: the check is done with Ax, Px, Aty, which now take A dx, P dx, A'dyh
+                ProfScope ps(prof, cat_inf, 2);
+                shared_deltas<T>(st, (int)n, (int)m, rowsN, rowsM, npanel, x, xp, y, yp, l, u, d_active, dxp, dyh);
+                check_products(dxp, dyh);
+                shared_certificates<T>(st, (int)n, (int)m, rowsN, rowsM, npanel, dxp, dyh, Ax, Px, Aty, q, l, u, d_active, kd, ke, cert_part, res_dev, inf_epsP, inf_epsD);
             }
             HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double) * (size_t)CP, hipMemcpyDeviceToHost, st));
             HIPC(hipStreamSynchronize(st));
@@ -188,6 +233,7 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         const double t2 = now_s();
         if (kd) { panel_rowscale<T>(st, x, kd, 1, rowsN, npanel, Px); get_panels(Px, xh, n, rowsN); }   // x = D x~ (through the check's scratch panel)
         else get_panels(x, xh, n, rowsN);
+        last_conv = conv;
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
             in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
@@ -206,7 +252,7 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     virtual void begin_solve(int warm, double rho, double sigma, double alpha) = 0;
     virtual void switch_rho(double rho, double sigma) = 0;                            // the family moved to `rho`: new factor, state that held the previous rho
     virtual void iterate(int lvl, double rho, double sigma, double alpha) = 0;        // one ADMM iteration of every active column, profiled at level `lvl`
-    virtual void check_products() = 0;                                                // Ax = A x, Px = P x, Aty = A'y
+    virtual void check_products(const T* xv, const T* yv) = 0;                        // Ax = A xv, Px = P xv, Aty = A'yv (the check's x, y; the certificates' dx, dyh)
 };
 
 // =================================================================================================================
@@ -253,6 +299,7 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         cat_bwd = prof.category("shared: backward sweep + x (MFMA panels)", s * ((double)n * (n + 1) / 2 + 5.0 * c * n));
         cat_pass = prof.category("shared: A x~ + row updates (MFMA panels)", s * ((double)m * n + c * (n + 8.0 * m)));
         cat_chk = prof.category("shared: check (A x, P x, A'y, norms)", s * (2.0 * m * n + (double)n * n + c * (8.0 * n + 6.0 * m)));
+        this->cat_inf = prof.category("shared: infeasibility (deltas, 3 products, sums)", s * (2.0 * m * n + (double)n * n + c * (10.0 * n + 10.0 * m)));
         cat_fac = prof.category("shared: factorisation at setup", s * ((double)m * n + 4.0 * n * n));
         cat_switch = prof.category("shared: rho switch (assemble, Cholesky, w)", s * (3.0 * n * n + 3.0 * c * m));
         cat_start = prof.category("shared: warm start (w, or A x -> z, w)", s * 3.0 * c * m);
@@ -314,6 +361,7 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         if (Ws) scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);         // the per-row rho scale reads the new A
         HIPC(hipStreamSynchronize(st));
         factor_valid = false; have_AA = false;                     // the cached product and the factor belong to the previous matrices
+        this->last_conv.clear();                                   // and a certificate to the scaling it was taken in
     }
     void set_rho_scale(const double* s) override {
         HIPC(hipSetDevice(device));
@@ -400,10 +448,12 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         { ProfLaunchScope ps(prof, cat_bwd, lvl); shared_panel<T>(st, SharedPanelOp::backward_x, a_bwd); }   // :137, L' x~ = y; SolveQuadraticProgram.jl:56-57
         { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, op_row, a_row); }                     // :139; SolveQuadraticProgram.jl:59-61
     }
-    void check_products() override {
-        shared_panel<T>(st, SharedPanelOp::product, a_ax);
-        shared_panel<T>(st, SharedPanelOp::product, a_px);
-        shared_panel<T>(st, SharedPanelOp::product, a_aty);
+    void check_products(const T* xv, const T* yv) override {
+        PanelArgs<T> ax = a_ax, px = a_px, aty = a_aty;
+        ax.B = xv; px.B = xv; aty.B = yv;
+        shared_panel<T>(st, SharedPanelOp::product, ax);
+        shared_panel<T>(st, SharedPanelOp::product, px);
+        shared_panel<T>(st, SharedPanelOp::product, aty);
     }
 };
 
@@ -458,6 +508,8 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         pf.cat_bwd = prof.category("sparse shared: backward levels (panels)", np * ents * (sz + 4) + sz * c * (ents + 3.0 * Ns));
         pf.cat_post = prof.category("sparse shared: post + update (panels)", 4.0 * Nd * np + sz * c * (2.0 * Nd + 5.0 * n + 8.0 * m));
         cat_chk = prof.category("sparse shared: check (A x, P x, A'y, norms)", np * (2.0 * annz + pnnz) * (sz + 4) + sz * c * ((2.0 * annz + pnnz) + 8.0 * n + 6.0 * m));
+        this->cat_inf = prof.category("sparse shared: infeasibility (deltas, 3 products, sums)",
+                                      np * (2.0 * annz + pnnz) * (sz + 4) + sz * c * ((2.0 * annz + pnnz) + 10.0 * n + 10.0 * m));
         cat_fac = prof.category("sparse shared: factorisation at setup", (sz + 4) * ents + sz * (pnnz + annz));
         cat_switch = prof.category("sparse shared: rho switch (numeric L D L')", (sz + 4) * ents + sz * (pnnz + annz));
         cat_start = prof.category("sparse shared: warm start (A x -> z)", np * annz * (sz + 4) + sz * c * (annz + m));
@@ -541,6 +593,7 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
             apply_equilibration(1, hd, he);
         }
         factor_valid = false;                                      // the numeric factor belongs to the previous values
+        this->last_conv.clear();                                   // and a certificate to the scaling it was taken in
     }
     void set_rho_scale(const double* sc) override {
         HIPC(hipSetDevice(device));
@@ -591,10 +644,10 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         ldl->iterate_panels(s, alpha, rho, sigma, rhs_ready, pf);                                   // LinearSystemSolvers.jl:37-40, SolveQuadraticProgram.jl:56-61
         rhs_ready = true;
     }
-    void check_products() override {
-        csr_panel<T>(st, A, x, (int)n, Ax, (int)m, npanel);
-        csr_panel<T>(st, P, x, (int)n, Px, (int)n, npanel);
-        csr_panel<T>(st, At, y, (int)m, Aty, (int)n, npanel);
+    void check_products(const T* xv, const T* yv) override {
+        csr_panel<T>(st, A, xv, (int)n, Ax, (int)m, npanel);
+        csr_panel<T>(st, P, xv, (int)n, Px, (int)n, npanel);
+        csr_panel<T>(st, At, yv, (int)m, Aty, (int)n, npanel);
     }
 };
 

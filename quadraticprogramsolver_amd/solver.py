@@ -39,6 +39,23 @@ class ConvergenceFlag(enum.IntEnum):
     convAdmm = 2
     convPrimDual = 3
 
+    @classmethod
+    def _missing_(cls, value):
+        """The two additive flags (below) are values of this type without being members of the reference's enum: iterating it still gives the reference's three."""
+        name = _ADDITIVE_FLAGS.get(value)
+        if name is None:
+            return None
+        flag = int.__new__(cls, value)
+        flag._name_, flag._value_ = name, value
+        return cls._value2member_map_.setdefault(value, flag)
+
+
+# Additive, returned only by a shared-matrix batch with set_infeasibility on (qps_set_shared_infeasibility): QPS_CONV_PRIMAL_INFEASIBLE, QPS_CONV_DUAL_INFEASIBLE.
+# ConvergenceFlag(4) is ConvergenceFlag.convPrimInfeasible, an int equal to 4 whose name is "convPrimInfeasible"; likewise 5.
+_ADDITIVE_FLAGS = {4: "convPrimInfeasible", 5: "convDualInfeasible"}
+ConvergenceFlag.convPrimInfeasible = ConvergenceFlag(4)
+ConvergenceFlag.convDualInfeasible = ConvergenceFlag(5)
+
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
@@ -378,6 +395,21 @@ class QuadraticProgramSharedBatch(_Handle):
         y = None if mY is None else self._rows(mY, "mY", self.m)
         ptr = lambda a: None if a is None else _dp(a)
         _lib.check(_lib.lib().qps_set_shared_dual(self._h, ptr(z), ptr(y)), self._h)
+
+    def set_infeasibility(self, ϵPrimInf=1e-4, ϵDualInf=1e-4):
+        """Per-column infeasibility certificates (qps_set_shared_infeasibility; OSQP §3.4), opt-in.  At a check, a column that CheckConvergence leaves running is
+        tested on the differences of its consecutive iterates: ``convPrimInfeasible`` (4) or ``convDualInfeasible`` (5) stops it there like any other flag, so one
+        column without a solution no longer holds the batch to ``numIterations`` nor steers the family-wide ρ.  Each tolerance is finite and >= 0 (OSQP: 1e-4);
+        ``None`` / ``False`` / ``0`` leaves that test off, both off is the default and the untouched path.  The setting stays with the handle."""
+        eps = [0.0 if (e is None or e is False) else float(e) for e in (ϵPrimInf, ϵDualInf)]
+        _lib.check(_lib.lib().qps_set_shared_infeasibility(self._h, eps[0], eps[1]), self._h)
+
+    def certificate(self):
+        """(mDY [count x m], mDX [count x n]) of the last ``solve`` (qps_get_shared_certificate): row b of mDY is the projected δy of column b if it ended with
+        ``convPrimInfeasible``, row b of mDX its δx if it ended with ``convDualInfeasible``, zeros otherwise; the caller's units, unnormalised."""
+        DY, DX = np.zeros((self.count, self.m)), np.zeros((self.count, self.n))
+        _lib.check(_lib.lib().qps_get_shared_certificate(self._h, _dp(DY), _dp(DX)), self._h)
+        return DY, DX
 
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
