@@ -226,7 +226,8 @@ int32_t qps_solve_batch(qps_handle h, double *x_inout, const qps_params *params,
  * x = the iterate at its own stopping iteration.  Arguments are validated as by qps_create_dense, for every column, before a device is needed.
  * count is limited to 65535, as for qps_create_dense_batch (QPS_ERR_BAD_DIMENSION beyond).
  * QPS_ERR_UNSUPPORTED (qps_last_error names the reason): m = 0 or n padded beyond 16384 (fp64) / 32768 (fp32) at creation; adptRho != 0 (one
- * factor needs one rho), polish != 0 or a trsvBlock other than 0 or >= n at qps_solve_batch -- the handle stays usable afterwards.
+ * factor needs one rho), polish != 0 or a trsvBlock other than 0 or >= n at qps_solve_batch -- the handle stays usable afterwards
+ * (qps_params.polish stays refused; qps_polish_shared / qps_set_shared_polish run the step).
  * qps_update_shared_vectors replaces q, l and / or u of every column (a NULL pointer keeps the array); the factorisation does not depend on
  * them, so a following qps_solve_batch with reuseFactor = 1 and unchanged (rho, sigma) does not factorise again. */
 int32_t qps_create_dense_shared_batch(int64_t count, int64_t n, int64_t m, const double *P, int64_t ldp, const double *A, int64_t lda,
@@ -279,7 +280,8 @@ int32_t qps_set_shared_adaptive_rho(qps_handle h, int32_t mode /* 0 fixed rho, 1
  * The loop then runs unchanged on D P D, E A D, D q, E l, E u; in the caller's variables that is the ADMM loop with sigma_j = sigma / D_j^2 and rho_i = rho E_i^2,
  * so the iterates differ from those of an unscaled solve.  The warm start goes in as D^-1 x, the result comes back as D x~, qps_get_dual returns E^-1 z~ and E y~, and
  * the convergence check -- hence resPrim / resDual, the per-column flags and the family-wide rho rule -- sees the unscaled norms, as in OSQP.  With a rho scale set,
- * row i runs with rho * scale[i] on the scaled rows.  adptRho and polish stay refused.
+ * row i runs with rho * scale[i] on the scaled rows.  adptRho and qps_params.polish stay refused; qps_polish_shared / qps_set_shared_polish run the polishing step
+ * on the scaled data.
  * Range: after the passes and before anything is modified, the largest and the smallest non-zero scaled matrix magnitude have to be normal numbers of the handle's
  * type (this matters for fp32); otherwise QPS_ERR_UNSUPPORTED and the handle stays as it was.  Vector entries are not range-checked: a scaled bound that overflows
  * is a bound at infinity.
@@ -308,7 +310,7 @@ int32_t qps_get_shared_equilibration(qps_handle h, double *d_out /* [n] or NULL 
  * After a qps_solve_batch that returned an error the stored z and y are unspecified until qps_set_shared_dual or a mode-0 solve.
  * QPS_ERR_BAD_ARGUMENT: a NULL handle, a mode outside 0..2 (judged before the kind of handle), or a NaN / Inf entry of z or y (before a device is needed; the
  * handle keeps its state).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch.
- * Out of scope: stand-alone handles, qps_create_dense_batch, ProxQP handles (qps_proxqp_set_state serves them) and polishing. */
+ * Out of scope: stand-alone handles, qps_create_dense_batch, ProxQP handles (qps_proxqp_set_state serves them). */
 int32_t qps_set_shared_warm_start(qps_handle h, int32_t mode /* 0 z = y = 0 (default), 1 the stored z and y, 2 z = A x and the stored y */);
 int32_t qps_set_shared_dual(qps_handle h, const double *z, const double *y);   /* [count][m] each; NULL keeps that array */
 
@@ -350,6 +352,29 @@ int32_t qps_set_shared_dual(qps_handle h, const double *z, const double *y);   /
 int32_t qps_set_shared_infeasibility(qps_handle h, double epsPrimInf, double epsDualInf);   /* 0, 0 = off (default); OSQP: 1e-4, 1e-4 */
 int32_t qps_get_shared_certificate(qps_handle h, double *dy /* [count][m] or NULL */, double *dx /* [count][n] or NULL */);
 
+/* Polishing on a shared-matrix batch handle (dense or sparse), opt-in.  qps_params.polish stays refused on these handles; the two entry points below run the step.
+ * Per column it is the step of qps_polish: active sets from the sign of y, g = [-q; l(L); u(U)], iterative refinement of K t = g with MINRES on K + blkdiag(delta I,
+ * -delta I), x = t(1:n) only where the column's last MINRES call converged.  All columns advance in lockstep on 16-column panels, so P, A and A' are read once per
+ * MINRES iteration for 16..32 columns; every column has its own MINRES state, stops on its own residual and is frozen from then on.  In refinement round jj the
+ * columns still refining run MINRES together; a column whose call ended with flag 1 leaves with its x kept, the others add the correction and go on.  Inner
+ * products are added in an order that depends on n and m only: a column of a batch equals the same data in a batch of one bit for bit, report included.
+ * qps_polish_shared uses numItrPolish, delta, epsMinres and numItrMinres of *params and nothing else of it.  It works before any solve, ignores rho, the rho scale,
+ * the family rule, the warm-start mode and the certificate setting, and leaves the stored z and y, the factor and everything else the handle keeps untouched: a
+ * following qps_solve_batch, warm-started or not, is bit for bit what it would have been.  y = NULL takes the y the handle holds (the last qps_solve_batch or
+ * qps_set_shared_dual; zero on a fresh handle: every mask is empty and the system is P t = -q).  reports [count]: flag, refinements, minresIterations, relres,
+ * numActiveLower and numActiveUpper are per column, seconds is the wall time of the whole batch's step.
+ * qps_set_shared_polish(h, 1): every qps_solve_batch ends with that step on its own x and y, on every column whose flag is not QPS_CONV_PRIMAL_INFEASIBLE or
+ * QPS_CONV_DUAL_INFEASIBLE (those keep polishFlag = -1 and their x); polishFlag, polishIterations and tPolish of each qps_info are filled (tPolish: wall time of the
+ * whole batch's step, not part of tLoop), the stored z and y stay those of the loop, and x_inout is what qps_polish_shared(h, x, NULL, params, ...) would have made
+ * of the unpolished result, bit for bit.  0 (the default): as without it, polishFlag = -1, polishIterations = 0, tPolish = 0.  The switch stays with the handle.
+ * Equilibration: the step runs on the scaled data the handle holds, as OSQP's does -- x~ = D^-1 x and y~ = E^-1 y go in, x = D t~_x comes out, all exact powers of
+ * two -- so delta regularises, and epsMinres bounds the residual of, the system in the scaled variables.  The active sets do not change (the scaling is positive).
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, x_inout or params, a NaN / Inf in x or y, a delta that is not finite, a NaN epsMinres, an `on` other than 0 or 1 (before
+ * a device is needed; the handle is unchanged).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch.
+ * Out of scope: qps_solve_batch_multi, ProxQP handles, a per-column delta, a preconditioner. */
+int32_t qps_polish_shared(qps_handle h, double *x_inout, const double *y, const qps_params *params, qps_polish_report *reports);
+int32_t qps_set_shared_polish(qps_handle h, int32_t on /* 1: every qps_solve_batch ends with the step; 0 (default): as without it */);
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads
@@ -361,7 +386,7 @@ int32_t qps_get_shared_certificate(qps_handle h, double *dy /* [count][m] or NUL
  * check, flag, iteration count and residuals; x, z, y are the iterates of its own stopping iteration.  A column of a batch equals the same data in a batch of
  * one bit for bit.
  * qps_solve_batch refuses with QPS_ERR_UNSUPPORTED (the handle stays usable): adptRho != 0, polish != 0, a linsys other than QPS_LINSYS_AUTO or
- * QPS_LINSYS_KKT_LDL.  trsvBlock and loopVariant are accepted and without effect (they steer dense sweeps).  With reuseFactor = 1 and unchanged (rho, sigma)
+ * QPS_LINSYS_KKT_LDL (qps_params.polish stays refused; qps_polish_shared / qps_set_shared_polish run the step).  trsvBlock and loopVariant are accepted and without effect (they steer dense sweeps).  With reuseFactor = 1 and unchanged (rho, sigma)
  * nothing is factorised again, also after qps_update_shared_vectors.  qps_info per column: sweepVariant = 0, trsvBlock = 0, numRefactor = 0.
  * Environment, read once per handle at creation: QPS_LDL_PANEL_SPR = 1 | 4 | 16 forces that many 16-lane strips per factor row in every level of the sweeps
  * (unset: chosen per level from the mean row length). */

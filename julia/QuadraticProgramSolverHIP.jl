@@ -456,10 +456,10 @@ end
 EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
 
 function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIterations = 5000, ϵAbs = 1e-6, ϵRel = 1e-6, ρ = 1, σ = 1e-6, α = 1.6,
-    fctrΡ = 5, numItrConv = 25, reuseFactor::Bool = false)
+    fctrΡ = 5, numItrConv = 25, reuseFactor::Bool = false, numItrPolish = 10, δ = 1e-6, ϵMinres = 1e-6, numItrMinres = 500)
     h = sb.h; count = sb.count
     size(mX) == (sb.n, count) || throw(DimensionMismatch("mX must be n x count: the library reads and writes count columns of length n"))
-    prm = QpsParams(numIterations, 0, numItrConv, 10, 500, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, 1e-6, fctrΡ, 1e-6, 1e-6, 1000, 0, 0, 0)
+    prm = QpsParams(numIterations, 0, numItrConv, numItrPolish, numItrMinres, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, δ, fctrΡ, ϵMinres, 1e-6, 1000, 0, 0, 0)   # the polishing kwargs act under SharedBatchSetPolish!
     buf = Vector{UInt8}(undef, count * sizeof(QpsInfo))
     GC.@preserve mX buf _check(ccall((:qps_solve_batch, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
                                      h, mX, Ref(prm), buf), h)
@@ -486,6 +486,32 @@ function SharedBatchCertificate(sb::SharedBatchHip)
     mDY = zeros(sb.m, sb.count); mDX = zeros(sb.n, sb.count)
     GC.@preserve mDY mDX _check(ccall((:qps_get_shared_certificate, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h, mDY, mDX), h)
     return mDY, mDX
+end
+
+# Polishing (SolveQuadraticProgram.m:289-325) of every column at once (qps_polish_shared): mX is n x count and column b is replaced only where the returned report
+# has flag == 0; mY (m x count) is the multiplier, `nothing` takes the y the handle holds (the last SharedBatchSolve! or SharedBatchSetDual!).  With equilibration on
+# δ and ϵMinres act in the scaled variables.  Returns one QpsPolishReport per column (seconds: wall time of the whole batch's step).
+function SharedBatchPolish!(sb::SharedBatchHip, mX::Matrix{Float64}, mY::Union{Nothing, Matrix{Float64}} = nothing; numItrPolish = 10, δ = 1e-6, ϵMinres = 1e-6,
+    numItrMinres = 500)
+    h = sb.h; count = sb.count
+    size(mX) == (sb.n, count) || throw(DimensionMismatch("mX must be n x count: the library reads and writes count columns of length n"))
+    (mY === nothing || size(mY) == (sb.m, count)) || throw(DimensionMismatch("mY must be m x count"))
+    prm = QpsParams(5000, 0, 25, numItrPolish, numItrMinres, 0, 0, 0, 1e-6, 1e-6, 1.0, 1e-6, 1.6, δ, 5.0, ϵMinres, 1e-6, 1000, 0, 0, 0)
+    buf = Vector{UInt8}(undef, count * sizeof(QpsPolishReport))               # qps_polish_report records land here (QpsPolishReport is mutable: not stored inline)
+    pY = mY === nothing ? Ptr{Float64}(C_NULL) : pointer(mY)
+    GC.@preserve mX mY buf _check(ccall((:qps_polish_shared, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
+                                        h, mX, pY, Ref(prm), buf), h)
+    vRep = [QpsPolishReport() for _ in 1:count]
+    for b in 1:count
+        unsafe_copyto!(Ptr{UInt8}(pointer_from_objref(vRep[b])), pointer(buf, (b - 1) * sizeof(QpsPolishReport) + 1), sizeof(QpsPolishReport))
+    end
+    return vRep
+end
+
+# on = true: every SharedBatchSolve! ends with the polishing step on its own x and y (qps_set_shared_polish); false (the default): as without it
+function SharedBatchSetPolish!(sb::SharedBatchHip, on::Bool = true)
+    _check(ccall((:qps_set_shared_polish, LIBQPS), Int32, (Ptr{Cvoid}, Int32), sb.h, on ? 1 : 0), sb.h)
+    return nothing
 end
 
 SharedBatchDestroy(sb::SharedBatchHip) = ccall((:qps_destroy, LIBQPS), Int32, (Ptr{Cvoid},), sb.h)

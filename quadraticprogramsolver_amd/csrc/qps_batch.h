@@ -11,6 +11,7 @@ namespace qps {
 struct SharedFamilyOps {
     int family_rho = 0;               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule (one factor, hence one rho to move)
     int warm_start = 0;               // qps_set_shared_warm_start: 0 z = y = 0, 1 the stored (z, y), 2 z = A x and the stored y
+    int polish_on = 0;                // qps_set_shared_polish: 1 = every solve_batch ends with the polishing step on its own x and y
     std::vector<int> eq_kd, eq_ke;    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
     virtual ~SharedFamilyOps() {}
     virtual void update_vectors(const double* q, const double* l, const double* u) = 0;   // [count][n], [count][m], [count][m]; NULL keeps that array
@@ -19,6 +20,8 @@ struct SharedFamilyOps {
     virtual void set_dual(const double* z, const double* y) = 0;                          // [count][m] each, finite; NULL keeps that array
     virtual void set_infeasibility(double epsPrimInf, double epsDualInf) = 0;             // qps_set_shared_infeasibility: finite, >= 0; both 0 = off
     virtual void get_certificate(double* dy, double* dx) = 0;                             // [count][m], [count][n]; either may be NULL
+    // qps_polish_shared: x [count][n] (replaced where reports[b].flag == 0), y [count][m] or NULL = the stored y, reports [count] or NULL; finite arrays
+    virtual void polish(double* x, const double* y, const qps_params& p, qps_polish_report* reports) = 0;
 };
 
 struct BatchSolverBase {

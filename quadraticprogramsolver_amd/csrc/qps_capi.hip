@@ -1264,6 +1264,32 @@ QPS_API int32_t qps_get_shared_certificate(qps_handle hh, double* dy, double* dx
     return guarded(h, [&] { fam->get_certificate(dy, dx); });
 }
 
+QPS_API int32_t qps_polish_shared(qps_handle hh, double* x, const double* y, const qps_params* p, qps_polish_report* reports) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (!x) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_polish_shared: x_inout is NULL");
+    if (!p) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_polish_shared: params is NULL");
+    if (!std::isfinite(p->delta) || std::isnan(p->epsMinres)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_polish_shared: delta must be finite and epsMinres must not be NaN");
+    const char* other = "qps_polish_shared: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) polish all columns at once (qps_polish serves a stand-alone handle, qps_params.polish a qps_create_dense_batch handle)";
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    const int64_t c = h->fused_batch->count;
+    if (!all_finite(x, c * h->n, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_polish_shared: x contains NaN/Inf (the handle is unchanged)");
+    if (y && !all_finite(y, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_polish_shared: y contains NaN/Inf (the handle is unchanged)");
+    return guarded(h, [&] { fam->polish(x, y, *p, reports); });
+}
+
+QPS_API int32_t qps_set_shared_polish(qps_handle hh, int32_t on) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (on != 0 && on != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_polish: on must be 0 (qps_solve_batch ends at the loop) or 1 (it ends with the polishing step)");
+    const char* other = "qps_set_shared_polish: only shared-matrix batch handles (qps_create_dense_shared_batch, qps_create_csc_shared_batch) take this switch (other handles: qps_params.polish)";
+    SharedFamilyOps* fam = shared_family_of(h);
+    if (!fam) return fail_with(h, QPS_ERR_UNSUPPORTED, other);
+    fam->polish_on = on;
+    return QPS_OK;
+}
+
 QPS_API int32_t qps_set_shared_equilibration(qps_handle hh, int32_t passes) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");

@@ -192,6 +192,33 @@ template <typename T> void scale_rows(hipStream_t st, const T* src, const T* sca
 // epilogue leaves behind, re-formed after a switch of the family rho (qps_set_shared_adaptive_rho)
 template <typename T> void panel_w(hipStream_t st, const T* z, const T* y, const int* active, const T* rho_row, T rho, int MP, int npanel, T* w);
 
+// ---- polishing step of the shared-matrix batches (k_shared_polish.hip): the kernels of qps_polish.hip on panels, one MINRES per column in lockstep ----------
+// A KKT vector is [npanel][rowsN][16] followed by [npanel][rowsM][16] (multiplier block at full length, 0/1 mask).  The products A v_x, P v_x, A'wl with
+// wl = mask v_lambda come from the handle's check_products; SharedPolishProducts names their panels.  State: [2][16 npanel], ping-ponged by shared_polish_step.
+// live / take: one int per column.  pa / pb: 16 npanel * shared_polish_blocks doubles each (one partial per column and workgroup, added in workgroup order).
+struct SharedPolishState { double beta, oldb, dbar, epsln, phibar, cs, sn, bnorm, tol, alfa; int itn, done, flag, maxit; };
+struct SharedPolishGeom { int n = 0, m = 0, rowsN = 0, rowsM = 0, npanel = 0; };
+template <typename T> struct SharedPolishProducts { const T* mask = nullptr; T* wl = nullptr; const T *Ax = nullptr, *Px = nullptr, *Aty = nullptr; };
+int shared_polish_blocks(int rowsN, int rowsM);   // workgroups per panel: from the vector length alone, so a column's sums do not depend on the batch around it
+// mask, g = [-q; l or u or 0] and counts[2 b] = numL, counts[2 b + 1] = numU (zero-filled by the caller) from the sign of y       SolveQuadraticProgram.m:293-299
+template <typename T>
+void shared_polish_setup(hipStream_t st, const SharedPolishGeom& g, const T* q, const T* l, const T* u, const T* y, T* mask, T* gv, int* counts);
+template <typename T> void shared_polish_wl(hipStream_t st, const SharedPolishGeom& g, const T* mask, const T* v, T* wl);   // wl = mask v_lambda, every column
+// rhs = g - K t on the live columns, from the products of (t_x, wl)
+template <typename T>
+void shared_polish_rhs(hipStream_t st, const SharedPolishGeom& g, const int* live, const T* gv, const T* t, const SharedPolishProducts<T>& k, T* rhs);
+// MINRES start from x0 (products of (x0_x, wl)): r1 = r2 = b - KK x0, w0 = w1 = 0, both halves of `state`; a column that is not live is born done
+template <typename T>
+void shared_polish_begin(hipStream_t st, const SharedPolishGeom& g, const int* live, T delta, const T* b, const T* x0, const SharedPolishProducts<T>& k, T* r1,
+                         T* r2, T* w0, T* w1, double* pa, double* pb, SharedPolishState* state, double tol, int maxit);
+// one MINRES iteration of every column that is not done, after the products of (r2_x, wl): c = KK r2, the Lanczos vector over r1 (and wl = mask of it for the
+// next product), w over w1, x += phi w, nxt = the next states.  The caller then swaps r1 / r2, w1 / w2 and cur / nxt.
+template <typename T>
+void shared_polish_step(hipStream_t st, const SharedPolishGeom& g, SharedPolishState* cur, SharedPolishState* nxt, T delta, const SharedPolishProducts<T>& k,
+                        T* c, T* r1, T* r2, T* w1, const T* w2, T* x, double* pa, double* pb);
+template <typename T> void shared_polish_add(hipStream_t st, const SharedPolishGeom& g, const int* live, const SharedPolishState* state, T* t, T* tt);   // t += tt (:319)
+template <typename T> void shared_polish_select(hipStream_t st, const SharedPolishGeom& g, const int* take, const T* t, T* x);   // x = t_x where take (:322-325)
+
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);
 template <typename T> void transpose_small(hipStream_t st, const T* A, int NP, int MP, T* At);

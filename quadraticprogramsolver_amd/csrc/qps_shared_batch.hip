@@ -8,6 +8,7 @@
 #include "dense_chol.h"
 #include "qps_batch.h"
 #include "qps_ldl.h"
+#include "qps_polish.h"
 #include "shared_family_rules.h"
 #include "spmv_layout.h"
 
@@ -231,6 +232,13 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         HIPC(hipStreamSynchronize(st));
         prof.harvest();
         const double t2 = now_s();
+        std::vector<PolishReport> pol; double tpol = 0;
+        if (polish_on) {                                                                            // qps_set_shared_polish: the step on this solve's own x and y
+            std::vector<int> take(count);
+            for (int b = 0; b < count; ++b) take[b] = conv[b] != QPS_CONV_PRIMAL_INFEASIBLE && conv[b] != QPS_CONV_DUAL_INFEASIBLE;
+            polish_panels(y, x, p, take, pol);
+            tpol = now_s() - t2;
+        }
         if (kd) { panel_rowscale<T>(st, x, kd, 1, rowsN, npanel, Px); get_panels(Px, xh, n, rowsN); }   // x = D x~ (through the check's scratch panel)
         else get_panels(x, xh, n, rowsN);
         last_conv = conv;
@@ -239,9 +247,105 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
             in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
             in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
             in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
-            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = 0;
+            in.polishFlag = -1; in.polishIterations = 0; in.tPolish = tpol;
+            if (polish_on) { in.polishFlag = pol[b].flag; in.polishIterations = pol[b].minresIterations; }
             in.trsvBlock = info_trsv_block; in.sweepVariant = info_sweep_variant; in.sweepGaveUp = 0; in.cgExplicit = 0;
         }
+    }
+
+    // qps_polish_shared: the step from the caller's x and y (NULL: the y the handle holds), in work panels of this call; nothing the handle keeps is written
+    void polish(double* xh, const double* yh, const qps_params& p, qps_polish_report* reports) override {
+        HIPC(hipSetDevice(device));
+        DeviceOwner wm;
+        T* xb = wm.dalloc<T>((int64_t)CP * rowsN, st); T* yb = yh ? wm.dalloc<T>((int64_t)CP * rowsM, st) : nullptr;
+        put_panels(xh, xb, n, rowsN);
+        if (kd) panel_rowscale<T>(st, xb, kd, -1, rowsN, npanel, xb);                               // x~ = D^-1 x
+        if (yh) { put_panels(yh, yb, m, rowsM); if (kd) panel_rowscale<T>(st, yb, ke, -1, rowsM, npanel, yb); }   // y~ = E^-1 y
+        std::vector<PolishReport> pol;
+        polish_panels(yh ? yb : y, xb, p, std::vector<int>(), pol);
+        if (kd) panel_rowscale<T>(st, xb, kd, 1, rowsN, npanel, xb);                                // x = D t~_x
+        std::vector<double> xo((size_t)count * (size_t)n);
+        get_panels(xb, xo.data(), n, rowsN);
+        for (int b = 0; b < count; ++b) {
+            if (pol[b].flag == 0) std::copy(xo.begin() + (size_t)b * n, xo.begin() + (size_t)(b + 1) * n, xh + (size_t)b * n);   // :322-325; other columns keep every bit
+            if (!reports) continue;
+            qps_polish_report& r = reports[b];
+            r.flag = pol[b].flag; r.refinements = pol[b].refinements; r.minresIterations = pol[b].minresIterations; r.numActiveLower = pol[b].numLower;
+            r.numActiveUpper = pol[b].numUpper; r.reserved0 = 0; r.relres = pol[b].relres; r.seconds = pol[b].seconds;
+        }
+    }
+    // SolveQuadraticProgram.m:289-325 for the columns of `take` (empty: all), all at once, on the data the handle holds (the scaled data while the equilibration
+    // is on): ypan are rowsM panels, xpan rowsN panels that take t_x where the column's last MINRES call converged.  K v comes from check_products -- the
+    // matrices are read once per MINRES iteration for all columns of a panel pair -- and k_shared_polish.hip does the rest.  The columns advance in lockstep:
+    // in round jj those still refining form g - K t and run MINRES together, the host reading the per-column states every 8 iterations; a column whose call
+    // ended with flag 1 leaves with its x kept (:316-318), the others add tt and go on.  The work panels live for this call only.
+    void polish_panels(const T* ypan, T* xpan, const qps_params& p, const std::vector<int>& take, std::vector<PolishReport>& reps) {
+        const double t0 = now_s();
+        reps.assign(count, PolishReport());
+        if (p.numItrPolish <= 0) return;                                                            // :292
+        SharedPolishGeom g; g.n = (int)n; g.m = (int)m; g.rowsN = rowsN; g.rowsM = rowsM; g.npanel = npanel;
+        const int64_t N = (int64_t)CP * (rowsN + rowsM), ML = (int64_t)CP * rowsM; const int nblk = shared_polish_blocks(rowsN, rowsM);
+        DeviceOwner wm;
+        T* gv = wm.dalloc<T>(9 * N + 2 * ML, st);
+        T *t = gv + N, *tt = t + N, *rhs = tt + N, *c = rhs + N, *r1 = c + N, *r2 = r1 + N, *w1 = r2 + N, *w2 = w1 + N, *mask = w2 + N, *wl = mask + ML;   // t = tt = 0 (:307-308)
+        double* pa = wm.dalloc<double>(2 * (int64_t)CP * nblk, st); double* pb = pa + (int64_t)CP * nblk;
+        SharedPolishState* state = wm.dalloc<SharedPolishState>(2 * (int64_t)CP, st);
+        int* counts = wm.dalloc<int>(3 * (int64_t)CP, st); int* live_dev = counts + 2 * CP;
+        SharedPolishState* hs = wm.pinned<SharedPolishState>((size_t)CP); int* hi = wm.pinned<int>(3 * (size_t)CP);
+        std::vector<int> live(CP, 0);
+        int nlive = 0;
+        for (int b = 0; b < count; ++b) nlive += live[b] = take.empty() || take[b];
+        auto push_live = [&] {
+            for (int b = 0; b < CP; ++b) hi[2 * CP + b] = live[b];
+            HIPC(hipMemcpyAsync(live_dev, hi + 2 * CP, sizeof(int) * CP, hipMemcpyHostToDevice, st));
+            HIPC(hipStreamSynchronize(st));
+        };
+        shared_polish_setup<T>(st, g, q, l, u, ypan, mask, gv, counts);                             // :293-299
+        HIPC(hipMemcpyAsync(hi, counts, sizeof(int) * 2 * CP, hipMemcpyDeviceToHost, st));
+        push_live();
+        const SharedPolishProducts<T> k{mask, wl, Ax, Px, Aty};
+        const T delta = (T)p.delta;
+        for (int jj = 0; jj < p.numItrPolish && nlive > 0; ++jj) {                                  // :314
+            shared_polish_wl<T>(st, g, mask, t, wl);
+            check_products(t, wl);
+            shared_polish_rhs<T>(st, g, live_dev, gv, t, k, rhs);                                   // g - K t
+            shared_polish_wl<T>(st, g, mask, tt, wl);
+            check_products(tt, wl);                                                                 // KK x0, x0 = the tt of the previous round
+            shared_polish_begin<T>(st, g, live_dev, delta, rhs, tt, k, r1, r2, w1, w2, pa, pb, state, p.epsMinres, p.numItrMinres);   // :315
+            shared_polish_wl<T>(st, g, mask, r2, wl);
+            int cur = 0, launched = 0;
+            auto any_running = [&] {
+                HIPC(hipMemcpyAsync(hs, state + (int64_t)cur * CP, sizeof(SharedPolishState) * (size_t)CP, hipMemcpyDeviceToHost, st));
+                HIPC(hipStreamSynchronize(st));
+                for (int b = 0; b < count; ++b) if (live[b] && !hs[b].done) return true;
+                return false;
+            };
+            bool running = any_running();
+            while (running && launched < p.numItrMinres) {
+                for (int burst = std::min(8, p.numItrMinres - launched); burst > 0; --burst) {
+                    check_products(r2, wl);                                                         // KK y (= beta KK v)
+                    shared_polish_step<T>(st, g, state + (int64_t)cur * CP, state + (int64_t)(cur ^ 1) * CP, delta, k, c, r1, r2, w1, w2, tt, pa, pb);
+                    std::swap(r1, r2); std::swap(w1, w2);                                           // r2 = the new Lanczos vector, w2 = the new w
+                    cur ^= 1; ++launched;
+                }
+                running = any_running();
+            }
+            for (int b = 0; b < count; ++b) {
+                if (!live[b]) continue;
+                const SharedPolishState& s = hs[b];
+                PolishReport& r = reps[b];
+                r.flag = s.done ? s.flag : 1; r.minresIterations += s.itn; r.refinements = jj + 1; r.relres = s.bnorm == 0.0 ? 0.0 : s.phibar / s.bnorm;
+                if (r.flag) { live[b] = 0; --nlive; }                                               // :316-318
+            }
+            push_live();
+            if (nlive > 0) shared_polish_add<T>(st, g, live_dev, state + (int64_t)cur * CP, t, tt); // :319
+        }
+        for (int b = 0; b < count; ++b) live[b] = reps[b].flag == 0;
+        push_live();
+        shared_polish_select<T>(st, g, live_dev, t, xpan);                                          // :322-325
+        HIPC(hipStreamSynchronize(st));
+        const double secs = now_s() - t0;
+        for (int b = 0; b < count; ++b) { reps[b].numLower = hi[2 * b]; reps[b].numUpper = hi[2 * b + 1]; reps[b].seconds = secs; }
     }
 
   protected:
@@ -252,7 +356,8 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     virtual void begin_solve(int warm, double rho, double sigma, double alpha) = 0;
     virtual void switch_rho(double rho, double sigma) = 0;                            // the family moved to `rho`: new factor, state that held the previous rho
     virtual void iterate(int lvl, double rho, double sigma, double alpha) = 0;        // one ADMM iteration of every active column, profiled at level `lvl`
-    virtual void check_products(const T* xv, const T* yv) = 0;                        // Ax = A xv, Px = P xv, Aty = A'yv (the check's x, y; the certificates' dx, dyh)
+    // Ax = A xv, Px = P xv, Aty = A'yv for arbitrary panels (the check's x, y; the certificates' dx, dyh; the polishing step's v_x, mask v_lambda); usable outside a solve
+    virtual void check_products(const T* xv, const T* yv) = 0;
 };
 
 // =================================================================================================================
@@ -275,7 +380,7 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
     // The per-row rho scale here: Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so M = PI + rho Ws'Ws comes out of the same symmetric
     // product and a change of the base rho alone only re-assembles.  Equilibration: At holds D A' E beside D P D and E A D.
     T *Ws = nullptr, *rs_sqrt = nullptr;
-    PanelArgs<T> a_rhs, a_fwd, a_bwd, a_row, a_ax, a_px, a_aty; SharedPanelOp op_row = SharedPanelOp::rows_zy;   // the launches of the running solve
+    PanelArgs<T> a_rhs, a_fwd, a_bwd, a_row; SharedPanelOp op_row = SharedPanelOp::rows_zy;   // the launches of the running solve
 
     SharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_) : B(dev, cnt, n_, m_, roundup(n_, 64), roundup(m_, 64)) {
         NP = this->rowsN; MP = this->rowsM;
@@ -433,7 +538,6 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         a_row.z = z; a_row.zp = zp; a_row.y = y; a_row.w = w; a_row.l = l; a_row.u = u; a_row.alpha = (T)alpha; a_row.rho = (T)rho;
         a_row.rho_row = rs_rho; a_row.rho1_row = rs_rho1;
         op_row = scaled ? SharedPanelOp::rows_zy_scaled : SharedPanelOp::rows_zy;
-        a_ax = product_args(A, NP, MP, NP, x, Ax); a_px = product_args(P, NP, NP, NP, x, Px); a_aty = product_args(At, MP, NP, MP, y, Aty);
     }
     void switch_rho(double rho, double sigma) override {
         const bool scaled = !rho_scale.empty();
@@ -449,11 +553,9 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         { ProfLaunchScope ps(prof, cat_pass, lvl); shared_panel<T>(st, op_row, a_row); }                     // :139; SolveQuadraticProgram.jl:59-61
     }
     void check_products(const T* xv, const T* yv) override {
-        PanelArgs<T> ax = a_ax, px = a_px, aty = a_aty;
-        ax.B = xv; px.B = xv; aty.B = yv;
-        shared_panel<T>(st, SharedPanelOp::product, ax);
-        shared_panel<T>(st, SharedPanelOp::product, px);
-        shared_panel<T>(st, SharedPanelOp::product, aty);
+        shared_panel<T>(st, SharedPanelOp::product, product_args(A, NP, MP, NP, xv, Ax));
+        shared_panel<T>(st, SharedPanelOp::product, product_args(P, NP, NP, NP, xv, Px));
+        shared_panel<T>(st, SharedPanelOp::product, product_args(At, MP, NP, MP, yv, Aty));
     }
 };
 

@@ -411,6 +411,26 @@ class QuadraticProgramSharedBatch(_Handle):
         _lib.check(_lib.lib().qps_get_shared_certificate(self._h, _dp(DY), _dp(DX)), self._h)
         return DY, DX
 
+    def polish(self, mX, mY=None, *, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
+        """The polishing step (SolveQuadraticProgram.m:289-325) for every column at once (qps_polish_shared), from the primals ``mX`` [count x n] (row b is replaced
+        in place only where its report has flag 0) and the multipliers ``mY`` [count x m]; ``None`` takes the y the handle holds (the last ``solve`` or
+        ``set_dual``).  Returns the list of report dicts, keys as ``QuadraticProgram.polish`` (``seconds``: wall time of the whole batch's step).  Nothing the handle
+        keeps is touched; with equilibration on, ``δ`` and ``ϵMinres`` act in the scaled variables."""
+        if not isinstance(mX, np.ndarray) or mX.dtype != np.float64 or not mX.flags.c_contiguous or mX.shape != (self.count, self.n):
+            raise ValueError("mX must be a contiguous float64 array of shape (count, numElements) (it is updated in place)")
+        y = None if mY is None else self._rows(mY, "mY", self.m)
+        p = _lib.default_params()
+        p.numItrPolish, p.delta, p.epsMinres, p.numItrMinres = int(numItrPolish), float(δ), float(ϵMinres), int(numItrMinres)
+        reps = (_lib.QpsPolishReport * self.count)()
+        _lib.check(_lib.lib().qps_polish_shared(self._h, _dp(mX), None if y is None else _dp(y), C.byref(p), reps), self._h)
+        return [r.as_dict() for r in reps]
+
+    def set_polish(self, on=True):
+        """``True``: every ``solve`` ends with the polishing step on its own x and y (qps_set_shared_polish), with ``numItrPolish``, ``δ``, ``ϵMinres`` and
+        ``numItrMinres`` of that ``solve``; ``polishFlag`` / ``polishIterations`` / ``tPolish`` of the info dicts report it per column, and a column that ended with
+        an infeasibility flag is left alone.  ``False`` (the default): as without it.  ``polish=True`` of ``solve`` stays refused."""
+        _lib.check(_lib.lib().qps_set_shared_polish(self._h, 1 if on else 0), self._h)
+
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
         """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts), as ``QuadraticProgramBatch.solve``.  ``mX`` (optional) holds the warm starts."""
