@@ -452,12 +452,6 @@ template <typename T> struct DevVec {
     void upload(const std::vector<T>& h, StagedUploader& up) { alloc((int64_t)h.size(), up.st); if (!h.empty()) up.copy(p, h.data(), sizeof(T) * h.size()); }
 };
 
-int pick_lpr(int64_t nnz, int rows) {
-    if (rows <= 0) return 1;
-    const double avg = (double)nnz / rows;
-    return avg <= 2.0 ? 1 : (avg <= 12.0 ? 4 : (avg <= 96.0 ? 16 : (avg <= 1024.0 || rows > 2048 ? 64 : 256)));
-}
-
 template <typename T> struct SparseLdlImpl : SparseLdl<T> {
     hipStream_t st; LdlSymbolic S;
     DevVec<int> rp, ci, cp, ri, cj, csc2csr, ksrc, dposP, perm, iperm, ent_q, ent_dst;
@@ -466,7 +460,7 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
     DevVec<int> fail;
     std::vector<int> group_ptr; int KC = 16, GS = 1, nb = 64; bool tail_signed = false;   // Schur complement: groups of GS K-slices of KC columns
     DevVec<T> slabs;
-    std::vector<int> lpr_fwd, lpr_bwd; int lpr_tail = 1;
+    std::vector<int> lpr_fwd, lpr_bwd; int lpr_tail = 1;   // lanes per row / column of the scalar sweeps, per level and for the tail rows (pick_lpr, ldl_symbolic.h)
     const T *row_rho = nullptr, *row_rho1 = nullptr;   // set_row_rho: rho_i, 1 / rho_i by the caller's row (not owned)
     DevVec<T> bP, tbP, tuP, txP; int npanel = 0; std::vector<int> spr_fwd, spr_bwd; int spr_tail = 1;   // panel forms (panels_prepare)
 

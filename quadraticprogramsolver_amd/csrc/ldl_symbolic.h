@@ -59,4 +59,12 @@ std::vector<int> line_dissection_order(int N, const std::vector<std::vector<int>
 LdlSymbolic ldl_analyze(int n, int m, const int64_t* Pcp, const int64_t* Pri, const int64_t* Acp, const int64_t* Ari, int index_base,
                         int max_tail, int min_level_width, int max_levels);
 
+// Lanes per factor row (forward sweep) or column (backward sweep) of the scalar sweep kernels k_ldl_fwd / k_ldl_bwd<T, LPR> for a level (or the tail rows) of
+// `rows` rows holding `nnz` entries of L: by the mean length; 256 lanes = one workgroup per row, only while the level stays within 2048 workgroups.
+inline int pick_lpr(int64_t nnz, int rows) {
+    if (rows <= 0) return 1;
+    const double avg = (double)nnz / rows;
+    return avg <= 2.0 ? 1 : (avg <= 12.0 ? 4 : (avg <= 96.0 ? 16 : (avg <= 1024.0 || rows > 2048 ? 64 : 256)));
+}
+
 }  // namespace qps

@@ -133,6 +133,25 @@ SHIM_API int lt_ldl_analyze(int n, int m, const int64_t* Pcp, const int64_t* Pri
         return 0;
     } catch (const std::exception&) { return -1; }
 }
+// The shape of the analysis that the sweep dispatch of k_ldl.hip reads (tests/ldl_band_cases.py): level_ptr[levels + 1], rp_at / cp_at [levels + 1] =
+// rp / cp at every level boundary (cap entries each; -2 when the analysis has more levels than that), misc[8] = {N, Ns, Nt, ldt, rp[N] - rp[Ns], tail rows with a
+// positive sign, with a negative sign, sparse columns that reach into the tail}.  Returns the level count, -1 on an exception.
+SHIM_API int lt_ldl_level_shape(int n, int m, const int64_t* Pcp, const int64_t* Pri, const int64_t* Acp, const int64_t* Ari, int base, int max_tail, int min_level,
+                                int max_levels, int cap, int64_t* level_ptr, int64_t* rp_at, int64_t* cp_at, int64_t* misc) {
+    try {
+        const LdlSymbolic s = ldl_analyze(n, m, Pcp, Pri, Acp, Ari, base, max_tail, min_level, max_levels);
+        const int L = (int)s.level_ptr.size() - 1;
+        if (L + 1 > cap) return -2;
+        for (int l = 0; l <= L; ++l) { const int c = s.level_ptr[(size_t)l]; level_ptr[l] = c; rp_at[l] = s.rp[(size_t)c]; cp_at[l] = s.cp[(size_t)c]; }
+        int64_t pos = 0, neg = 0, ntc = 0;
+        for (int i = s.Ns; i < s.N; ++i) (s.sign[(size_t)i] > 0 ? pos : neg) += 1;
+        for (int j = 0; j < s.Ns; ++j) if (s.cp[(size_t)j + 1] > s.cp[(size_t)j] && s.ri[(size_t)s.cp[(size_t)j + 1] - 1] >= s.Ns) ++ntc;   // rows sorted: the last one decides
+        misc[0] = s.N; misc[1] = s.Ns; misc[2] = s.Nt; misc[3] = s.ldt; misc[4] = (int64_t)s.rp[(size_t)s.N] - s.rp[(size_t)s.Ns]; misc[5] = pos; misc[6] = neg; misc[7] = ntc;
+        return L;
+    } catch (const std::exception&) { return -1; }
+}
+// the lane-group rule of the scalar sweeps as k_ldl.hip calls it (ldl_symbolic.h)
+SHIM_API int lt_pick_lpr(int64_t nnz, int rows) { return pick_lpr(nnz, rows); }
 // The two host rules of the shared-matrix batches (shared_family_rules.h) as the solvers call them.  res: 8 doubles per column ([0..3] the four norms), active: one
 // word per column; step: the exponent step of one equilibration pass for the norm v, *clamp (may be NULL) the bound of the exponents.
 SHIM_API double lt_family_rho_proposal(const double* res, const int* active, int count, double rho, double rhorho) {
