@@ -938,10 +938,9 @@ template <typename T> struct SparseSolver : SolverBase {
         if (!ldl) {
             if (n + m > 2000000000LL) throw QpsError(QPS_ERR_BAD_DIMENSION, "KKT matrix too large for the sparse direct plugin");
             // read at every analysis (once per handle), not once per process: the limits are part of a handle's layout
-            const char *e1 = getenv("QPS_LDL_MAX_TAIL"), *e2 = getenv("QPS_LDL_MIN_LEVEL"), *e3 = getenv("QPS_LDL_MAX_LEVELS");
-            const int max_tail = e1 ? atoi(e1) : 8192, min_level = e2 ? atoi(e2) : 64, max_levels = e3 ? atoi(e3) : 4096;
+            const LdlLimits lim = ldl_limits_from_env();
             LdlSymbolic sym;
-            try { sym = ldl_analyze((int)n, (int)m, hPcp.data(), hPri.data(), hAcp.data(), hAri.data(), 0, max_tail, min_level, max_levels); }
+            try { sym = ldl_analyze((int)n, (int)m, hPcp.data(), hPri.data(), hAcp.data(), hAri.data(), 0, lim.max_tail, lim.min_level_width, lim.max_levels); }
             catch (const std::runtime_error& e) { throw QpsError(QPS_ERR_UNSUPPORTED, e.what()); }
             ldl = make_sparse_ldl<T>(st, std::move(sym), hPnz.data(), (int64_t)hPnz.size(), hAnz.data(), (int64_t)hAnz.size());
             ldl_valid = false;

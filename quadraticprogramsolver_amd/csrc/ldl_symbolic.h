@@ -18,6 +18,7 @@
 //     one dense Nt x Nt matrix and factorised / solved by the dense kernels.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -58,6 +59,13 @@ std::vector<int> line_dissection_order(int N, const std::vector<std::vector<int>
 // Throws std::runtime_error when the factor would not fit (nnz(L) beyond 2^31 - 1 or the level count beyond max_levels).
 LdlSymbolic ldl_analyze(int n, int m, const int64_t* Pcp, const int64_t* Pri, const int64_t* Acp, const int64_t* Ari, int index_base,
                         int max_tail, int min_level_width, int max_levels);
+
+// The limits of ldl_analyze as the environment sets them, read at every call: QPS_LDL_MAX_TAIL, QPS_LDL_MIN_LEVEL, QPS_LDL_MAX_LEVELS.
+struct LdlLimits { int max_tail, min_level_width, max_levels; };
+inline LdlLimits ldl_limits_from_env() {
+    const char *e1 = getenv("QPS_LDL_MAX_TAIL"), *e2 = getenv("QPS_LDL_MIN_LEVEL"), *e3 = getenv("QPS_LDL_MAX_LEVELS");
+    return {e1 ? atoi(e1) : 8192, e2 ? atoi(e2) : 64, e3 ? atoi(e3) : 4096};
+}
 
 // Lanes per factor row (forward sweep) or column (backward sweep) of the scalar sweep kernels k_ldl_fwd / k_ldl_bwd<T, LPR> for a level (or the tail rows) of
 // `rows` rows holding `nnz` entries of L: by the mean length; 256 lanes = one workgroup per row, only while the level stays within 2048 workgroups.

@@ -1,5 +1,6 @@
-// qps_batch.h -- what the batch handles share between qps_capi.hip (handle plumbing, BatchedDenseSolver) and qps_shared_batch.hip (the shared-matrix family):
-// the base of every fused batch solver, the one interface the qps_*_shared_* entry points talk to, the factories of the family, and the panelled matrix upload.
+// qps_batch.h -- what the batch handles share between qps_capi.hip (handle plumbing), qps_dense_batch.hip (BatchedDenseSolver) and qps_shared_batch.hip (the
+// shared-matrix family): the base of every fused batch solver, the one interface the qps_*_shared_* entry points talk to, the factories of all three, and the
+// panelled matrix upload.
 #pragma once
 #include "ldl_symbolic.h"
 #include "qps_internal.h"
@@ -31,6 +32,11 @@ struct BatchSolverBase {
     virtual void get_dual(double* z, double* y) = 0;   // [count][m] each
     virtual SharedFamilyOps* shared_family() { return nullptr; }   // the shared-matrix batches only
 };
+
+// `count` independent dense QPs of one shape in lock step (qps_dense_batch.hip): P [count][n * n], A [count][m * n] column-major, q [count][n], l / u [count][m],
+// validated by the caller.  The loaded solver, or nullptr when the fused pass does not cover the shape (count = 1, m = 0, n beyond its limit).
+BatchSolverBase* make_dense_batch(int device, int dtype, int count, int64_t n, int64_t m, const double* P, const double* A, const double* q, const double* l,
+                                  const double* u);
 
 struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
     LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;

@@ -265,5 +265,8 @@ struct SolverBase {
 SolverBase* make_sparse_solver(int device, int64_t n, int64_t m, int dtype, const int64_t* Pcp, const int64_t* Pri,
                                const double* Pnz, const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* q,
                                const double* l, const double* u, int index_base);
+// dense handle, Cholesky path (qps_dense.hip): column-major P (n x n, ld ldp) and A (m x n, ld lda), validated by the caller
+SolverBase* make_dense(int device, int64_t n, int64_t m, int dtype, const double* P, int64_t ldp, const double* A, int64_t lda, const double* q, const double* l,
+                       const double* u);
 
 }  // namespace qps

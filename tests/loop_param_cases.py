@@ -4,7 +4,7 @@
 
 How each route was confirmed (the handle reports ``sweepVariant`` and ``cgExplicit`` only, so the GPU tests assert those and the rest is read off
 the dispatch code):
-  reg          qps_capi.hip DenseSolver::solve_once takes the single launch (sweepVariant == 4) when admm_small_supported and loopVariant == 0;
+  reg          qps_dense.hip DenseSolver::solve_once takes the single launch (sweepVariant == 4) when admm_small_supported and loopVariant == 0;
                k_small.hip admm_small picks k_admm_small_reg for NP in {64, 128} with MP / 64 <= 2 (fp64) / 4 (fp32): (64, 128) in both types.
   lds          the same branch with MP / 64 beyond that bound: k_admm_small.  fp64 (64, 130) has MP / 64 = 3 (the (64, 250) draws do not
                reach 1e-3 within 3000 iterations at rho = 0.1); fp32 needs (64, 300), MP / 64 = 5.
@@ -13,7 +13,7 @@ the dispatch code):
   fused_graph_small   (64, 128) with loopVariant = 2: the same loop at one 64-column block.
   fused_eager  (200, 330) with numItrConv = 2: use_graph needs numItrConv >= 3, so every iteration is enqueued by the host.
   unfused      loopVariant = 1: linear_solve + k_admm_update + the three-product check (LinearSystemSolvers.jl:134-139 order).
-  batch_small  BatchedDenseSolver::solve_batch: NP = 64, MP = 128 passes admm_small_batch_supported -> k_admm_small_reg_batch, one workgroup per QP.
+  batch_small  qps_dense_batch.hip BatchedDenseSolver::solve_batch: NP = 64, MP = 128 passes admm_small_batch_supported -> k_admm_small_reg_batch, one workgroup per QP.
   batch_lockstep   NP = 192 is neither 64 nor 128: the lock-step loop (k_apass with PassBatch, batched check).
   shared       SharedBatchSolver: EPI 2 / 3 epilogues of k_panel and k_shared_decide; count 18 = a full panel of 16 and a ragged one of 2.  The
                STAGED form of k_panel is the same EPI code in the same template and needs matrices above 32 MiB: left out here, it is covered at
