@@ -1,5 +1,5 @@
-// k_proxqp_rows.h -- row-wise kernels and the host decision of the ProxQP.jl iteration, shared by the dense (qps_proxqp.hip) and the sparse
-// (k_sparse.hip: SparseProxQpSolver) solver of that form.  G = [A; C] stacked, g = [b; d], dual = [y; z], s on the inequality rows.
+// k_proxqp_rows.h -- row-wise kernels and the host decision of the ProxQP.jl iteration, shared by the dense and the sparse
+// solver of that form (qps_proxqp.hip: ProxQpSolver, SparseProxQpSolver).  G = [A; C] stacked, g = [b; d], dual = [y; z], s on the inequality rows.
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -1,4 +1,5 @@
-// k_sparse.hip -- CSR path: SpMV kernels and the device-resident matrix-free CG plugin.
+// k_sparse.hip -- CSR path: SpMV kernels and the device-resident matrix-free CG plugin, with the objects that launch them (qps_spmv.h).  The solvers
+// built on them are elsewhere: SparseSolver in qps_sparse.hip, SparseProxQpSolver in qps_proxqp.hip.
 //
 // Reference: LinOpCgInit / LinOpCg! (LinearSystemSolvers.jl:145-186): the reduced operator
 //     u = P w + rho A'(A w) + sigma w                                   (:152-157)
@@ -14,21 +15,14 @@
 // reads 32 bytes per batch; iterations enqueued past convergence return at their first instruction.
 #include <algorithm>
 
-#include "qps_internal.h"
-#include "qps_kernels.h"
-#include "qps_ldl.h"
-#include "qps_polish.h"
-#include "qps_proxqp.h"
-#include "k_proxqp_rows.h"
+#include "qps_spmv.h"
 #include "wave_reduce.h"
-#include "spmv_layout.h"
 #include <hip/hip_ext.h>
 
 namespace qps {
 
 namespace {
 
-struct CgState { double res2, prev2, tol, uc; int iters, done, maxiter, pad; };   // two copies, ping-ponged per CG iteration
 using layout::STREAM_NNZ;           // non-zeros streamed per workgroup (256 threads x 4); the layouts themselves are built in spmv_layout.cpp
 
 __device__ __forceinline__ double block_sum_256(double v, double* sh) {
@@ -748,786 +742,302 @@ __global__ __launch_bounds__(256) void k_refresh_values(int64_t count, const int
     if (i < count) { const int k = src[i]; dst[i] = k >= 0 ? va[k] : T(0); }
 }
 
-struct Csr {
-    int nrows = 0; int64_t nnz = 0; int* rp = nullptr; int* ci = nullptr; void* va = nullptr; int* rb = nullptr; int nblocks = 0;
-    // column-blocked copy (k_spmv_blk): nblk CSR blocks back to back; used when `blocked`
-    bool blocked = false; int ncols = 0, nblk = 0, wpb = 0; int* brp = nullptr; unsigned short* bci = nullptr; void* bva = nullptr;
-    int* task_ptr = nullptr; int4* tasks = nullptr; int per = 1, lpr4 = 0; void* partial = nullptr;
-    int* lr_ptr = nullptr; int4* lr_desc = nullptr;   // rows with more than BCHUNK entries in one block: (row, first entry, end entry, 0), [nblk + 1] ranges
-    // sliced form (k_spmv_sell): units of 64 lanes x E entries; bci / bva then hold only the long rows' entries
-    bool sell = false; int nsl = 0, win = layout::SIGMA, nwin = 0, staged = 0; int* wg_ptr = nullptr; int* sl_off = nullptr; unsigned short* sl_perm = nullptr; void* s_cols = nullptr; void* s_vals = nullptr;
-    // value refresh of a matrix with a frozen pattern (the explicit reduced matrix): where every slot of s_vals / bva came from in `va`
-    int* src = nullptr; int64_t src_n = 0; int* lsrc = nullptr; int64_t lsrc_n = 0;
-};
-
-template <typename T> struct SparseSolver : SolverBase {
-    // destroyed in reverse: what works on the stream (`ldl` below, `up`), the buffers, the stream lease, then the base's Profiler
-    StreamLease lease; DeviceOwner mem; std::unique_ptr<StagedUploader> up;   // `up` lives for the duration of the constructor only
-    Csr A, At, P, PA;   // PA = [P; A] stacked, column-blocked only: P u and A u of the CG operator from ONE pass over u
-    // ItrSolCgInit / ItrSolCg! (LinearSystemSolvers.jl:110-142): the explicit reduced matrix mL = mPI + rho mAA on a frozen pattern; ONE product per CG iteration
-    Csr Lm; T *L_vP = nullptr, *L_vAA = nullptr, *L_dg = nullptr;
-    int explicit_state = 0;          // 0 undecided, 1 built, -1 declined (too dense to pay, or its inputs were released)
-    bool cg_explicit = false; bool L_valid = false; double L_rho = 0, L_sigma = 0; int num_L_builds = 0;
-    T *q = nullptr, *l = nullptr, *u = nullptr, *x = nullptr, *xp = nullptr, *z = nullptr, *zp = nullptr, *y = nullptr;
-    T *xx = nullptr, *zz = nullptr, *w = nullptr, *tt = nullptr, *cu = nullptr, *cu2 = nullptr, *cr = nullptr, *cc = nullptr, *tm = nullptr;
-    T *Ax = nullptr, *Px = nullptr, *Aty = nullptr;
-    double *part_uc = nullptr, *part_rr = nullptr; int part_uc_cap = 0; CgState* state = nullptr; CgState* state_host = nullptr;
-    unsigned long long* scratch = nullptr; double* res_dev = nullptr; double* res_host = nullptr; double* stage = nullptr;
-    int nb_n = 0, nb_op = 0; int64_t cg_total = 0; int last_cg = 4;
-    double eps_pcg = 1e-6; int itr_pcg = 1000;
-    int cat_spmv, cat_op, cat_vec, cat_chk, cat_ldl, cat_pa = 0, cat_at = 0; int prof_calls = 0;
-    // sparse direct KKT plugin (LinearSystemSolvers.jl:16-107): built on first use from canonical host copies of the caller's CSC
-    std::vector<int64_t> hPcp, hPri, hAcp, hAri; std::vector<double> hPnz, hAnz;
-    std::unique_ptr<SparseLdl<T>> ldl; bool ldl_valid = false; double ldl_rho = 0, ldl_sigma = 0; int plugin_kind = QPS_LINSYS_CG;
-    int num_factorizations = 0; bool ldl_unfit = false;   // ldl_unfit: the analysis refused this pattern once (AUTO then goes to CG without asking again)
-    // hipGraph replay of ONE plain iteration of the direct plugin (a dozen launches of 2-3 us of work each: the eager loop is bound by
-    // the host's launch rate).  Keyed by the scalars baked into the kernel arguments; every pointer of the loop is fixed.
-    struct IterGraph { double rho, sigma, alpha; hipGraphExec_t exec; };
-    std::vector<IterGraph> graphs; bool graphs_disabled = false;
-    void drop_graphs() { for (auto& gr : graphs) (void)hipGraphExecDestroy(gr.exec); graphs.clear(); }
-    hipGraphExec_t iter_graph(double rho, double sigma, double alpha) {
-        for (auto& gr : graphs) if (gr.rho == rho && gr.sigma == sigma && gr.alpha == alpha) return gr.exec;
-        if (graphs_disabled) return nullptr;
-        if (graphs.size() >= 8) drop_graphs();
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graphs_disabled = true; return nullptr; }
-        ldl->iterate(x, xp, q, z, zp, y, l, u, alpha, rho, sigma, true);                            // SolveQuadraticProgram.jl:54-61, right-hand side already in place
-        // nothing was enqueued while capturing, so a failure here just means: run this handle's iterations eagerly from now on
-        if (hipStreamEndCapture(st, &graph) != hipSuccess || graph == nullptr) { (void)hipGetLastError(); graphs_disabled = true; return nullptr; }
-        const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { (void)hipGetLastError(); graphs_disabled = true; return nullptr; }
-        graphs.push_back({rho, sigma, alpha, exec});
-        return exec;
+// partial[b][row] of M * x
+template <typename T> void spmv_blk(hipStream_t st, const Csr& M, const T* xin, const CgState* stt, CgFuse<T> fu = CgFuse<T>()) {
+    const LaunchTiming lt = g_launch_timing;   // profiled launch: the dispatch's own begin / end timestamps (qps_kernels.h)
+    g_launch_timing = LaunchTiming();
+    if (M.sell) {
+        const SellDims sd{M.nrows, M.ncols, M.nsl, M.wpb, M.win, M.nwin, M.staged};
+        using CV = typename SellOf<T>::CV; using V = typename VecOf<T>::type;
+        if (lt.start) hipExtLaunchKernelGGL((k_spmv_sell<T>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, lt.start, lt.stop, 0, sd, M.wg_ptr, M.sl_off, M.sl_perm,
+                                            static_cast<const CV*>(M.s_cols), static_cast<const V*>(M.s_vals), M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin,
+                                            static_cast<T*>(M.partial), stt, fu);
+        else hipLaunchKernelGGL((k_spmv_sell<T>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, sd, M.wg_ptr, M.sl_off, M.sl_perm, static_cast<const CV*>(M.s_cols),
+                                static_cast<const V*>(M.s_vals), M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu);
+        return;
     }
-
-    // Column-blocked copy of M: the sliced form (k_spmv_sell) when the host builder produces one, else the task form (k_spmv_blk).  The layouts are
-    // built by plain host code (spmv_layout.cpp, tested on the CPU against scipy); here they are only uploaded.
-    template <typename V> V* upload_array(const std::vector<V>& v, int64_t min_count = 1) {
-        V* d = mem.dalloc<V>(std::max<int64_t>((int64_t)v.size(), min_count), st);
-        if (!v.empty()) up->copy(d, v.data(), sizeof(V) * v.size());
-        return d;
-    }
-    void build_blocked(Csr& M, const layout::CsrHost& H, bool with_src = false) {
-        static const int wgs_env = [] { const char* e = getenv("QPS_SPMV_WGS"); return e ? atoi(e) : 0; }();
-        const int wgs = wgs_env > 0 ? wgs_env : 512;
-        M.ncols = H.ncols;
-        const char* e = getenv("QPS_SPMV_SELL");                     // read per handle: 0 = the task form (k_spmv_blk)
-        if (!(e && atoi(e) == 0)) {
-            layout::SellLayout<T> L;
-            const char* es = getenv("QPS_SPMV_STAGED");                 // read per handle: 0 = row sums stored lane by lane also when whole windows could be staged
-            if (layout::build_sell<T>(H, wgs, L, with_src, !(es && atoi(es) == 0))) {
-                M.nblk = L.nblk; M.nsl = L.nsl; M.wpb = L.wpb; M.win = L.win; M.nwin = L.nwin; M.staged = L.staged;
-                if (with_src) { M.src = upload_array(L.src); M.src_n = (int64_t)L.src.size(); M.lsrc = upload_array(L.lsrc); M.lsrc_n = (int64_t)L.lsrc.size(); }
-                M.s_cols = upload_array(L.cols); M.s_vals = upload_array(L.vals);
-                M.bci = upload_array(L.lci); M.bva = upload_array(L.lva);
-                M.sl_off = upload_array(L.sl_off); M.sl_perm = upload_array(L.perm); M.wg_ptr = upload_array(L.wg_ptr);
-                M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
-                M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);
-                M.blocked = true; M.sell = true;
-                return;
-            }
-        }
-        layout::TaskLayout<T> L;
-        try { layout::build_tasks<T>(H, wgs, L, with_src); }
-        catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
-        M.nblk = L.nblk; M.wpb = L.wpb; M.per = L.per; M.lpr4 = L.lpr4;
-        if (with_src) { M.src = upload_array(L.src); M.src_n = (int64_t)L.src.size(); }
-        M.brp = upload_array(L.brp); M.bci = upload_array(L.bci); M.bva = upload_array(L.bva);
-        M.task_ptr = upload_array(L.task_ptr); M.tasks = reinterpret_cast<int4*>(upload_array(L.tasks));
-        M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
-        M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);    // + 64: the dump slots of lanes without a row
-        M.blocked = true;
-    }
-    void upload_csr(Csr& M, const layout::CsrHost& H, bool with_src = false) {
-        M.nrows = H.nrows; M.nnz = (int64_t)H.ci.size();
-        {   // LDS-resident x pays once the gathers dominate; QPS_SPMV_BLOCKED = 1 / 0 forces the choice
-            // ... and only while the per-block partial sums (one per row and column block, written by the product and read back by its combine launch) stay below
-            // the matrix itself: a long banded matrix (n = 400 000: 56 column blocks) has 2.7 partial sums per entry -- 165 us per product where the CSR-stream
-            // kernel, whose gathers of x stay inside the band and hit the cache, needs a third of that
-            const char* e = getenv("QPS_SPMV_BLOCKED");
-            const int64_t nblk_ = (H.ncols + BlkOf<T>::CB - 1) / BlkOf<T>::CB;
-            const bool want = e ? atoi(e) != 0 : (M.nnz >= 200000 && nblk_ * (int64_t)H.nrows <= M.nnz);
-            if (want && H.nrows > 0 && H.ncols > 0) build_blocked(M, H, with_src);
-        }
-        M.rp = upload_array(H.rp); M.ci = upload_array(H.ci);
-        {
-            std::vector<T> v(H.va.begin(), H.va.end());
-            M.va = upload_array(v);
-        }
-        const std::vector<int> rbv = layout::stream_row_blocks(H);   // row blocks of the CSR-stream kernel
-        M.nblocks = (int)rbv.size() - 1;
-        M.rb = upload_array(rbv);
-    }
-    void upload_vec(const double* h, T* d, int64_t count) { HIPC(upload_staged<T>(st, stage, h, d, count)); }
-    void download_vec(const T* d, double* h, int64_t count) { HIPC(download_staged<T>(st, stage, d, h, count)); }
-    // ItrSolCgInit (LinearSystemSolvers.jl:110-122): mAA = mA' * mA, mPI = mP + sigma I, mL = mPI + rho * mAA, formed on the host ONCE per handle as three value
-    // arrays on the frozen pattern of mL (spmv_layout.cpp: reduced_matrix); returns whether the handle has it.  forced = an explicit QPS_LINSYS_CG_EXPLICIT request;
-    // otherwise the matrix is only formed when it pays -- A'A cheap to form (sum of squared row lengths) and mL no larger than 1.5 x the entries the matrix-free
-    // operator streams per application (nnz P + 2 nnz A).  BASELINE config 3 (unstructured, ~50 entries per row) fails the first test in O(m) and stays matrix-free.
-    bool explicit_prepare(bool forced) {
-        if (explicit_state != 0) {
-            if (forced && explicit_state < 0) throw QpsError(QPS_ERR_UNSUPPORTED, "QPS_LINSYS_CG_EXPLICIT: the reduced matrix of this handle cannot be formed (too many entries, or the handle's "
-                                                                                  "host copies were released to the direct plugin before the first CG request)");
-            return explicit_state > 0;
-        }
-        explicit_state = -1;
-        if (hPcp.empty() || hAcp.empty()) { if (forced) return explicit_prepare(true); return false; }   // released (the L D L' plugin was built first)
-        const int64_t pnnz = (int64_t)hPri.size(), annz = (int64_t)hAri.size();
-        layout::CsrHost Ph, Ah, Ath, Lh; std::vector<double> vAA, dg;
-        try {
-            Ph = layout::csc_as_transposed_csr(n, n, hPcp, hPri, hPnz);
-            layout::csc_to_csr_pair(m, n, hAcp, hAri, hAnz, Ah, Ath);
-            if (!forced && layout::ata_work(Ah) > 16 * (pnnz + annz)) return false;
-            const int64_t cap = forced ? 1900000000LL : (3 * (pnnz + 2 * annz)) / 2 + n;
-            if (!layout::reduced_matrix(Ph, Ah, Ath, cap, Lh, vAA, dg)) { if (forced) return explicit_prepare(true); return false; }
-        } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
-        up.reset(new StagedUploader(st));
-        upload_csr(Lm, Lh, true);
-        std::vector<T> t1(Lh.va.begin(), Lh.va.end()), t2(vAA.begin(), vAA.end()), t3(dg.begin(), dg.end());
-        L_vP = upload_array(t1); L_vAA = upload_array(t2); L_dg = upload_array(t3);
-        up.reset();
-        HIPC(hipStreamSynchronize(st));
-        if (dot_parts(Lm) + 64 > part_uc_cap) {                                                     // partials of dot(u, mL u): one per workgroup of the product's last launch
-            mem.release(part_uc); part_uc = nullptr;
-            part_uc_cap = dot_parts(Lm) + 64; part_uc = mem.dalloc<double>(part_uc_cap, st);
-        }
-        explicit_state = 1; L_valid = false;
-        return true;
-    }
-    // the values of mL for (rho, sigma): LinearSystemSolvers.jl:114 at Init, :127-129 on changedRho -- elementwise on the frozen pattern, then the column-blocked copy refreshed
-    void reduced_values(double rho, double sigma) {
-        if (L_valid && L_rho == rho && L_sigma == sigma) return;
-        const int64_t nnz = Lm.nnz;
-        if (nnz > 0) hipLaunchKernelGGL((k_build_reduced<T>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, L_vP, L_vAA, L_dg, (T)sigma, (T)rho, static_cast<T*>(Lm.va));
-        if (Lm.blocked) {
-            T* main_vals = static_cast<T*>(Lm.sell ? Lm.s_vals : Lm.bva);
-            if (Lm.src_n > 0) hipLaunchKernelGGL((k_refresh_values<T>), dim3((unsigned)((Lm.src_n + 255) / 256)), dim3(256), 0, st, Lm.src_n, Lm.src, static_cast<const T*>(Lm.va), main_vals);
-            if (Lm.sell && Lm.lsrc_n > 0)
-                hipLaunchKernelGGL((k_refresh_values<T>), dim3((unsigned)((Lm.lsrc_n + 255) / 256)), dim3(256), 0, st, Lm.lsrc_n, Lm.lsrc, static_cast<const T*>(Lm.va), static_cast<T*>(Lm.bva));
-        }
-        L_valid = true; L_rho = rho; L_sigma = sigma; ++num_L_builds;
-    }
-    // Which plugin a request means on a CSC handle, with the direct one factorised.  QPS_LINSYS_AUTO is the reference's modeAuto rule
-    // (SolveQuadraticProgram.jl:143-151, qps_linsys_auto) on this handle's sizes and non-zero counts, so that a C caller passing AUTO reaches the direct
-    // KKT plugin exactly when the reference would; when the factor then does not fit the level-scheduled plugin (QPS_ERR_UNSUPPORTED from the analysis) an
-    // AUTO request falls back to CG -- an EXPLICIT QPS_LINSYS_KKT_LDL request still fails loudly.
-    // A CG request is served by the explicit reduced matrix (ItrSolCg, one product per CG iteration) when the handle has one -- always for
-    // QPS_LINSYS_CG_EXPLICIT, for QPS_LINSYS_CG / AUTO when explicit_prepare finds that it pays (QPS_CG_EXPLICIT = 0 keeps those matrix-free) -- else by the
-    // matrix-free operator (LinOpCg / LinMapsCg, three products).
-    int resolve_cg(int linsys, double rho, double sigma) {
-        const char* e = getenv("QPS_CG_EXPLICIT");                                                  // read per request
-        cg_explicit = linsys == QPS_LINSYS_CG_EXPLICIT ? explicit_prepare(true) : (!(e && atoi(e) == 0) && explicit_prepare(false));
-        if (cg_explicit) reduced_values(rho, sigma);
-        return QPS_LINSYS_CG;
-    }
-    int resolve_kind(int linsys, double rho, double sigma, bool force) {
-        int kind = linsys;
-        if (linsys == QPS_LINSYS_AUTO) kind = qps_linsys_auto(n, m, P.nnz, A.nnz, 1);
-        if (kind != QPS_LINSYS_KKT_LDL) return resolve_cg(linsys, rho, sigma);
-        if (ldl_unfit && linsys == QPS_LINSYS_AUTO) return resolve_cg(linsys, rho, sigma);
-        try { ldl_prepare(rho, sigma, force); }
-        catch (const QpsError& e) {
-            if (linsys == QPS_LINSYS_AUTO && e.code == QPS_ERR_UNSUPPORTED) { ldl_unfit = true; return resolve_cg(linsys, rho, sigma); }
-            throw;
-        }
-        return QPS_LINSYS_KKT_LDL;
-    }
-    // LaLdlInit / QDLdlInit / FacLdlInit (LinearSystemSolvers.jl:16-24, :47-55, :78-86): ordering + symbolic once per handle, numeric per (rho, sigma)
-    void ldl_prepare(double rho, double sigma, bool force) {
-        if (!ldl) {
-            if (n + m > 2000000000LL) throw QpsError(QPS_ERR_BAD_DIMENSION, "KKT matrix too large for the sparse direct plugin");
-            // read at every analysis (once per handle), not once per process: the limits are part of a handle's layout
-            const LdlLimits lim = ldl_limits_from_env();
-            LdlSymbolic sym;
-            try { sym = ldl_analyze((int)n, (int)m, hPcp.data(), hPri.data(), hAcp.data(), hAri.data(), 0, lim.max_tail, lim.min_level_width, lim.max_levels); }
-            catch (const std::runtime_error& e) { throw QpsError(QPS_ERR_UNSUPPORTED, e.what()); }
-            ldl = make_sparse_ldl<T>(st, std::move(sym), hPnz.data(), (int64_t)hPnz.size(), hAnz.data(), (int64_t)hAnz.size());
-            ldl_valid = false;
-            for (auto* v : {&hPcp, &hPri, &hAcp, &hAri}) std::vector<int64_t>().swap(*v);           // the canonical host copies have served their purpose
-            std::vector<double>().swap(hPnz); std::vector<double>().swap(hAnz);                     // (a later CG request stays matrix-free: explicit_prepare)
-        }
-        if (force || !ldl_valid || ldl_rho != rho || ldl_sigma != sigma) {
-            ldl_valid = false;
-            ++num_factorizations;
-            ldl->factorize(rho, sigma);
-            ldl_valid = true; ldl_rho = rho; ldl_sigma = sigma;
-        }
-    }
-
-    SparseSolver(int dev, int64_t n_, int64_t m_, int dt, const int64_t* Pcp, const int64_t* Pri, const double* Pnz,
-                 const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* qh, const double* lh, const double* uh, int base) {
-        device = dev; n = n_; m = m_; dtype = dt; sparse = true;
-        HIPC(hipSetDevice(device));
-        st = prof.st = lease.acquire(device);   // recycled stream + pinned block (qps_internal.h)
-        void* const pinned = lease.res.pinned;
-        up.reset(new StagedUploader(st));
-        if (Pcp[n] - base > 2000000000LL || Acp[n] - base > 2000000000LL) throw QpsError(QPS_ERR_BAD_DIMENSION, "more than 2^31 non-zeros");
-        // canonical host copies first (sorted rows, duplicates summed, 0-based: a C caller's CSC need not be what Julia's sparse() guarantees);
-        // they feed the CSR copies below and, later, the analysis of the L D L' plugin
-        layout::canonical_csc(n, Pcp, Pri, Pnz, base, hPcp, hPri, hPnz);
-        layout::canonical_csc(n, Acp, Ari, Anz, base, hAcp, hAri, hAnz);
-        const int64_t pnnz = (int64_t)hPri.size(), annz = (int64_t)hAri.size();
-        layout::CsrHost Ph, Ah, Ath;
-        try {
-            Ph = layout::csc_as_transposed_csr(n, n, hPcp, hPri, hPnz);      // P: CSC == CSR (symmetric, full storage): its columns are its rows
-            layout::csc_to_csr_pair(m, n, hAcp, hAri, hAnz, Ah, Ath);        // rows of A by a counting sort; rows of A' are the columns of A == the CSC
-        } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
-        upload_csr(P, Ph);
-        upload_csr(At, Ath);
-        upload_csr(A, Ah);
-        const char* fuse_env = getenv("QPS_SPMV_FUSEPA");                 // 0: keep P, A, A' as three separate blocked products
-        if (m > 0 && P.blocked && A.blocked && At.blocked && pnnz + annz < 2000000000LL && !(fuse_env && atoi(fuse_env) == 0)) {
-            const layout::CsrHost Sh = layout::stack_rows(Ph, Ah);
-            PA.nrows = (int)(n + m); PA.nnz = pnnz + annz;
-            build_blocked(PA, Sh);
-        }
-        const int64_t nn = n + 64, mm = m + 64;
-        q = mem.dalloc<T>(nn, st); x = mem.dalloc<T>(nn, st); xp = mem.dalloc<T>(nn, st); xx = mem.dalloc<T>(nn, st); tt = mem.dalloc<T>(nn, st);
-        cu = mem.dalloc<T>(nn, st); cu2 = mem.dalloc<T>(nn, st); cr = mem.dalloc<T>(nn, st); cc = mem.dalloc<T>(nn, st); Px = mem.dalloc<T>(nn, st); Aty = mem.dalloc<T>(nn, st);
-        l = mem.dalloc<T>(mm, st); u = mem.dalloc<T>(mm, st); z = mem.dalloc<T>(mm, st); zp = mem.dalloc<T>(mm, st); y = mem.dalloc<T>(mm, st); zz = mem.dalloc<T>(mm, st);
-        w = mem.dalloc<T>(mm, st); tm = mem.dalloc<T>(mm, st); Ax = mem.dalloc<T>(mm, st);
-        nb_n = (int)((n + 255) / 256);
-        part_uc_cap = std::max(std::max(At.nblocks, P.nblocks), nb_n + (int)((m + 255) / 256)) + 64;
-        part_uc = mem.dalloc<double>(part_uc_cap, st); part_rr = mem.dalloc<double>(nb_n + 64, st);
-        state = reinterpret_cast<CgState*>(mem.dalloc<double>(16, st));
-        state_host = reinterpret_cast<CgState*>(pinned);                              // pinned block: CG state | check results
-        scratch = mem.dalloc<unsigned long long>(16, st); res_dev = mem.dalloc<double>(16, st);
-        res_host = reinterpret_cast<double*>(static_cast<char*>(pinned) + 128);
-        stage = mem.dalloc<double>(std::max(nn, mm) + 64, st);
-        upload_vec(qh, q, n); upload_vec(lh, l, m); upload_vec(uh, u, m);
-        const double s = sizeof(T);
-        auto spmv_bytes = [&](const Csr& M, int cols) { return (double)M.nnz * (s + 4) + M.nrows * 4.0 + s * (M.nrows + cols); };
-        cat_spmv = prof.category("spmv(A / A')", 0.5 * (spmv_bytes(A, (int)n) + spmv_bytes(At, (int)m)));
-        cat_op = prof.category("cg_iteration(A u, P u + rho A'. + sigma u, axpys)", spmv_bytes(A, (int)n) + spmv_bytes(At, (int)m) + spmv_bytes(P, (int)n) + s * 10.0 * n);
-        cat_vec = prof.category("admm_update", s * (3.0 * n + 7.0 * m));
-        cat_chk = prof.category("check_convergence", spmv_bytes(A, (int)n) + spmv_bytes(At, (int)m) + spmv_bytes(P, (int)n));
-        cat_ldl = prof.category("kkt_ldl_solve(rhs, level sweeps, dense tail, post)", 0.0);   // bytes are known once the factor exists
-        // the dominant kernel of the CG path: the stacked [P; A] product (nnz * 12 + rows * 4 + s * (rows + cols))
-        cat_pa = prof.category("spmv_blk([P;A] u, x block in LDS)", (double)(pnnz + annz) * (s + 4) + (double)(n + m) * 4.0 + s * (double)(n + m + n));
-        cat_at = prof.category("spmv_blk(A' v, x block in LDS)", spmv_bytes(At, (int)m));
-        // every fill and every upload above was enqueued on `st` (qps_internal.h, stream-ordering rule): nothing to wait for here
-        up.reset();
-    }
-    ~SparseSolver() override {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(st);
-        drop_graphs();
-        prof.release_events();
-    }
-
-    void spmv(const Csr& M, const T* xin, T* out, T a, const T* v0, T b0, const T* v1, T b1, const CgState* stt,
-              const T* dotv = nullptr, double* partial = nullptr) {
-        if (M.nblocks <= 0) return;
-        if (M.blocked) {
-            spmv_blk(M, xin, stt);
-            hipLaunchKernelGGL((k_spmv_combine<T>), dim3((M.nrows + 255) / 256), dim3(256), 0, st, M.nrows, static_cast<const T*>(M.partial), M.nblk, (int64_t)M.nrows, a,
-                               (const T*)nullptr, 0, (int64_t)0, T(0), v0, b0, v1, b1, out, dotv, partial, stt);
-            return;
-        }
-        hipLaunchKernelGGL((k_spmv_stream<T>), dim3(M.nblocks), dim3(256), 0, st, M.rb, M.rp, M.ci, static_cast<const T*>(M.va), xin, out, a,
-                           v0, b0, v1, b1, dotv, partial, stt);
-    }
-    // partial[b][row] of M * x
-    void spmv_blk(const Csr& M, const T* xin, const CgState* stt, CgFuse<T> fu = CgFuse<T>()) {
-        const LaunchTiming lt = g_launch_timing;   // profiled launch: the dispatch's own begin / end timestamps (qps_kernels.h)
-        g_launch_timing = LaunchTiming();
-        if (M.sell) {
-            const SellDims sd{M.nrows, M.ncols, M.nsl, M.wpb, M.win, M.nwin, M.staged};
-            using CV = typename SellOf<T>::CV; using V = typename VecOf<T>::type;
-            if (lt.start) hipExtLaunchKernelGGL((k_spmv_sell<T>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, lt.start, lt.stop, 0, sd, M.wg_ptr, M.sl_off, M.sl_perm,
-                                                static_cast<const CV*>(M.s_cols), static_cast<const V*>(M.s_vals), M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin,
-                                                static_cast<T*>(M.partial), stt, fu);
-            else hipLaunchKernelGGL((k_spmv_sell<T>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, sd, M.wg_ptr, M.sl_off, M.sl_perm, static_cast<const CV*>(M.s_cols),
-                                    static_cast<const V*>(M.s_vals), M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu);
-            return;
-        }
 #define QPS_BLK(LPR)                                                                                                                        \
-        do {                                                                                                                                \
-            if (lt.start) hipExtLaunchKernelGGL((k_spmv_blk<T, LPR>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, lt.start, lt.stop, 0, M.nrows, M.ncols, M.task_ptr, \
-                                                M.tasks, M.per, M.brp, M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu); \
-            else hipLaunchKernelGGL((k_spmv_blk<T, LPR>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, M.nrows, M.ncols, M.task_ptr, M.tasks, M.per, M.brp, M.bci, \
-                                    static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu);             \
-        } while (0)
-        if (M.lpr4) QPS_BLK(4); else QPS_BLK(8);
+    do {                                                                                                                                \
+        if (lt.start) hipExtLaunchKernelGGL((k_spmv_blk<T, LPR>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, lt.start, lt.stop, 0, M.nrows, M.ncols, M.task_ptr, \
+                                            M.tasks, M.per, M.brp, M.bci, static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu); \
+        else hipLaunchKernelGGL((k_spmv_blk<T, LPR>), dim3(M.wpb, M.nblk), dim3(BTHREADS), 0, st, M.nrows, M.ncols, M.task_ptr, M.tasks, M.per, M.brp, M.bci, \
+                                static_cast<const T*>(M.bva), M.lr_ptr, M.lr_desc, xin, static_cast<T*>(M.partial), stt, fu);             \
+    } while (0)
+    if (M.lpr4) QPS_BLK(4); else QPS_BLK(8);
 #undef QPS_BLK
-    }
-    int dot_parts(const Csr& M) const { return M.blocked ? (M.nrows + 255) / 256 : M.nblocks; }
-    // c = P u + rho A'(A u) + sigma u (LinearSystemSolvers.jl:152-157) as three streamed SpMVs; optional partials of dot(u, c)
-    void op_reduced(const T* uin, T* cout, double rho, double sigma, double* partial, const CgState* stt) {
-        if (m > 0 && P.blocked && A.blocked && At.blocked) {
-            // three blocked products; P u and A'(A u) share one combine launch that also forms the dot partials
-            spmv_blk(P, uin, stt);
-            spmv(A, uin, tm, T(1), nullptr, T(0), nullptr, T(0), stt);
-            spmv_blk(At, tm, stt);
-            hipLaunchKernelGGL((k_spmv_combine<T>), dim3(nb_n), dim3(256), 0, st, (int)n, static_cast<const T*>(P.partial), P.nblk, (int64_t)n, T(1),
-                               static_cast<const T*>(At.partial), At.nblk, (int64_t)n, (T)rho, uin, (T)sigma, (const T*)nullptr, T(0), cout, partial ? uin : nullptr, partial, stt);
-            return;
-        }
-        spmv(P, uin, cout, T(1), uin, (T)sigma, nullptr, T(0), stt, (m > 0) ? nullptr : uin, (m > 0) ? nullptr : partial);
-        if (m > 0) {
-            spmv(A, uin, tm, T(1), nullptr, T(0), nullptr, T(0), stt);
-            spmv(At, tm, cout, (T)rho, cout, T(1), nullptr, T(0), stt, uin, partial);
-        }
-    }
-    int op_parts() const { return (m > 0 && P.blocked && A.blocked && At.blocked) ? nb_n : (m > 0 ? dot_parts(At) : dot_parts(P)); }
-
-    // IterativeSolvers.cg!(xx, Op, tt; abstol = eps_pcg, maxiter = itr_pcg), xx warm started
-    int cg(double rho, double sigma) {
-        CgState* slot[2] = {state, state + 1};
-        int cur = 0;
-        // c = mL u: ONE product with the explicit matrix (ItrSolCg!, LinearSystemSolvers.jl:137) or the three of the matrix-free operator (:152-157)
-        auto apply_op = [&](const T* uin, T* cout, double* partial, const CgState* stt) {
-            if (cg_explicit) spmv(Lm, uin, cout, T(1), nullptr, T(0), nullptr, T(0), stt, partial ? uin : nullptr, partial);
-            else op_reduced(uin, cout, rho, sigma, partial, stt);
-        };
-        const int parts_op = cg_explicit ? dot_parts(Lm) : op_parts();
-        const bool fused_pa = PA.blocked && !cg_explicit;
-        apply_op(xx, cc, nullptr, nullptr);
-        T* ub[2] = {cu, cu2}; int ui = 0;                            // ub[ui] = current direction u
-        hipLaunchKernelGGL((k_cg_init<T>), dim3(nb_n), dim3(256), 0, st, (int)n, tt, cc, cr, ub[ui], part_rr);
-        hipLaunchKernelGGL(k_cg_init_final, dim3(1), dim3(256), 0, st, nb_n, part_rr, slot[cur], eps_pcg,
-                           sizeof(T) == 8 ? 1.4901161193847656e-08 : 3.4526698300124393e-04, itr_pcg);
-        // Launch batches: the first one is the previous call's iteration count (consecutive ADMM iterations need nearly the same number); every further
-        // one is what the measured contraction says is left (res_end / res_init over the iterations run so far), at least one and never more than doubles
-        // the total.  An iteration enqueued past convergence still costs four dispatches that return at the done flag: with "last + 1, then double" a
-        // sixth of the product dispatches of BASELINE config 3 were such no-ops (profiles/r03_z_bench_c3_kernel_stats.csv).
-        HIPC(hipMemcpyAsync(state_host + 1, slot[cur], sizeof(CgState), hipMemcpyDeviceToHost, st));   // the initial residual, read at the first synchronisation
-        int launched = 0, batch = std::max(1, std::min(last_cg, 64));
-        for (;;) {
-            for (int b = 0; b < batch; ++b) {
-                ProfScope ps(prof, cat_op, 2);
-                // fold the previous iteration's ||r||^2, publish the scalars into the other slot, u = r + beta u
-                if (fused_pa) {
-                    // [P; A] u with u = r + beta u_old formed while the x blocks are loaded; then A'(A u); ONE combine for c and dot(u, c)
-                    CgFuse<T> fu; fu.r = cr; fu.uold = ub[ui]; fu.unew = ub[ui ^ 1]; fu.part_rr = part_rr; fu.nparts = nb_n;
-                    fu.cur = slot[cur]; fu.nxt = slot[cur ^ 1]; fu.first = b == 0 ? 1 : 0;
-                    // level 1: the two products of the first CG iteration of every 8th cg() call are timed by their own dispatch timestamps
-                    const bool sample = prof.level == 2 || (prof.level == 1 && b == 0 && launched == 0 && prof_calls % 8 == 0);
-                    { ProfLaunchScope ps2(prof, cat_pa, sample ? 1 : 3); spmv_blk(PA, cr, nullptr, fu); }
-                    cur ^= 1; ui ^= 1;
-                    const T* pp = static_cast<const T*>(PA.partial);
-                    const int nb_m = (int)((m + 255) / 256);
-                    hipLaunchKernelGGL((k_cg_combine_pa<T>), dim3((unsigned)(nb_n + nb_m)), dim3(256), 0, st, (int)n, (int)m, nb_n, pp, PA.nblk, (int64_t)(n + m), ub[ui],
-                                       (T)sigma, (T)rho, cc, tm, part_uc, slot[cur]);                       // cc = P u, tm = A u, partials of dot(u, c)
-                    { ProfLaunchScope ps2(prof, cat_at, sample ? 1 : 3); spmv_blk(At, tm, slot[cur]); }
-                    hipLaunchKernelGGL((k_cg_combine_update<T>), dim3(nb_n), dim3(256), 0, st, (int)n, cc, static_cast<const T*>(At.partial), At.nblk, (int64_t)n, (T)rho,
-                                       (T)sigma, ub[ui], nb_n + nb_m, part_uc, xx, cr, part_rr, slot[cur]);
-                    continue;
-                } else {
-                    hipLaunchKernelGGL((k_cg_next_u<T>), dim3(nb_n), dim3(256), 0, st, (int)n, nb_n, part_rr, cr, ub[ui], slot[cur], slot[cur ^ 1], b == 0 ? 1 : 0);
-                    cur ^= 1;
-                    apply_op(ub[ui], cc, part_uc, slot[cur]);
-                }
-                hipLaunchKernelGGL((k_cg_update_xr<T>), dim3(nb_n), dim3(256), 0, st, (int)n, parts_op, part_uc, ub[ui], cc, xx, cr, part_rr, slot[cur]);
-            }
-            hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(256), 0, st, nb_n, part_rr, slot[cur]);   // fold the last iteration of the batch
-            launched += batch;
-            HIPC(hipMemcpyAsync(state_host, slot[cur], sizeof(CgState), hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-            prof.harvest();
-            if (state_host->done || launched >= itr_pcg) break;
-            {
-                const double r0 = std::sqrt(state_host[1].res2), r1 = std::sqrt(state_host->res2), tol = state_host->tol;
-                int left = std::max(launched, 1);                                                   // no usable rate: as many again
-                if (r1 > 0 && r0 > r1 && tol > 0 && r1 > tol) {
-                    const double per_it = std::log(r0 / r1) / std::max(1, state_host->iters);       // contraction per iteration so far
-                    left = (int)std::ceil(std::log(r1 / tol) / per_it);
-                }
-                batch = std::max(1, std::min(std::min(std::max(left, 2), std::max(launched, 2)), std::min(64, itr_pcg - launched)));   // (two at least: a synchronisation costs about one iteration)
-            }
-        }
-        last_cg = state_host->iters;
-        ++prof_calls;
-        cg_total += state_host->iters;
-        return state_host->iters;
-    }
-
-    // LinOpCg! body (LinearSystemSolvers.jl:176-181), or the direct KKT plugins' Sol! body (:37-40)
-    void linear_solve(double rho, double sigma) {
-        if (plugin_kind == QPS_LINSYS_KKT_LDL) {
-            ProfScope ps(prof, cat_ldl, 2);
-            ldl->solve(x, q, z, y, rho, sigma, xx, zz);
-            return;
-        }
-        if (m > 0) hipLaunchKernelGGL((k_axpby<T>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (int)m, (T)rho, z, T(-1), y, w);   // :176
-        {
-            ProfScope ps(prof, cat_spmv, 2);
-            if (m > 0) spmv(At, w, tt, T(1), x, (T)sigma, q, T(-1), nullptr);                        // :177-178
-            else hipLaunchKernelGGL((k_axpby<T>), dim3(nb_n), dim3(256), 0, st, (int)n, (T)sigma, x, T(-1), q, tt);
-        }
-        cg(rho, sigma);                                                                             // :179
-        {
-            ProfScope ps(prof, cat_spmv, 2);
-            if (m > 0) spmv(A, xx, zz, T(1), nullptr, T(0), nullptr, T(0), nullptr);                 // :181
-        }
-    }
-
-    void solve(double* xh, const qps_params& p, qps_info* info) override {
-        HIPC(hipSetDevice(device));
-        const double t0 = now_s();
-        double rho = p.rho; const double sigma = p.sigma, alpha = p.alpha;
-        eps_pcg = p.epsPcg; itr_pcg = p.numItrPcg;
-        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;
-        int convFlag = QPS_CONV_NUM_ITR;
-        if (p.linsys == QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "CSR handles offer QPS_LINSYS_CG, QPS_LINSYS_CG_EXPLICIT and QPS_LINSYS_KKT_LDL (create with dense_path=1 for the reduced Cholesky path)");
-        plugin_kind = resolve_kind(p.linsys, rho, sigma, !p.reuseFactor);                           // SolveQuadraticProgram.jl:36 LinSysSolInit (incl. the factorisation)
-        upload_vec(xh, x, n);
-        const size_t nb_ = sizeof(T) * (size_t)(n + 64), mb_ = sizeof(T) * (size_t)(m + 64);
-        HIPC(hipMemsetAsync(xp, 0, nb_, st)); HIPC(hipMemsetAsync(xx, 0, nb_, st));                 // LinOpCgInit: vXX = zeros (:147)
-        HIPC(hipMemsetAsync(z, 0, mb_, st)); HIPC(hipMemsetAsync(y, 0, mb_, st)); HIPC(hipMemsetAsync(zp, 0, mb_, st));
-        HIPC(hipStreamSynchronize(st));
-        const double t1 = now_s();
-        double rhorho = rho; int ii = 0, nref = 0; double resP = NAN, resD = NAN, tref = 0;
-        cg_total = 0; last_cg = 4;
-        const int NPv = (int)n, MPv = (int)m;
-        static const int graph_env = [] { const char* e = getenv("QPS_GRAPH"); return e ? atoi(e) : -1; }();
-        const bool use_graph = plugin_kind == QPS_LINSYS_KKT_LDL && prof.level == 0 && graph_env != 0;
-        bool ldl_rhs_ready = false;   // the fused post/update launch leaves the next right-hand side behind; stale after a rho switch
-        for (ii = 1; ii <= p.numIterations; ++ii) {
-            if (p.adptRho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {
-                rho = rhorho; ++nref;                                                               // matrix-free CG: nothing to rebuild
-                if (plugin_kind == QPS_LINSYS_CG && cg_explicit) { const double ta = now_s(); reduced_values(rho, sigma); tref += now_s() - ta; }   // changedΡ: LinearSystemSolvers.jl:127-129
-                if (plugin_kind == QPS_LINSYS_KKT_LDL) { const double ta = now_s(); ldl_prepare(rho, sigma, true); tref += now_s() - ta; ldl_rhs_ready = false; }   // changedΡ: numeric refactor only
-            }
-            if (plugin_kind == QPS_LINSYS_KKT_LDL && prof.level < 2) {
-                // direct plugin: sweeps + ONE launch for nu -> z~, the x / z / y updates and the next right-hand side (k_ldl_post_update)
-                if (use_graph && ldl_rhs_ready && ii % p.numItrConv != 0) {
-                    hipGraphExec_t ge = iter_graph(rho, sigma, alpha);
-                    if (ge) { HIPC(hipGraphLaunch(ge, st)); continue; }                             // a plain iteration: same kernels, same order
-                }
-                ldl->iterate(x, xp, q, z, zp, y, l, u, alpha, rho, sigma, ldl_rhs_ready);
-                ldl_rhs_ready = true;
-            } else {
-            linear_solve(rho, sigma);
-            {
-                ProfScope ps(prof, cat_vec, 2);
-                admm_update<T>(st, NPv, MPv, xx, zz, x, xp, z, zp, y, l, u, (T)alpha, (T)rho);
-            }
-            }
-            if (ii % p.numItrConv == 0) {
-                {
-                    ProfScope ps(prof, cat_chk, 2);
-                    if (m > 0) spmv(A, x, Ax, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                    spmv(P, x, Px, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                    if (m > 0) spmv(At, y, Aty, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                    else HIPC(hipMemsetAsync(Aty, 0, nb_, st));
-                    CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
-                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs);
-                }
-                HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-                HIPC(hipStreamSynchronize(st));
-                prof.harvest();
-                resP = res_host[0]; resD = res_host[1]; rhorho = res_host[4]; convFlag = (int)res_host[5];
-                if (convFlag != QPS_CONV_NUM_ITR) break;
-            }
-        }
-        HIPC(hipStreamSynchronize(st));
-        prof.harvest();
-        const double t2 = now_s();
-        PolishReport pr;
-        if (p.polish) polish_device(p, &pr);
-        download_vec(x, xh, n);
-        if (info) {
-            info->convFlag = convFlag; info->iterations = ii > p.numIterations ? p.numIterations : ii;
-            info->numRefactor = nref; info->cgIterations = (int)cg_total; info->rhoFinal = rho; info->rhoProposed = rhorho;
-            info->resPrim = resP; info->resDual = resD; info->tSetup = t1 - t0; info->tLoop = t2 - t1; info->tRefactor = tref;
-            info->trsvBlock = 0; info->sweepVariant = 0; info->sweepGaveUp = 0; info->cgExplicit = (plugin_kind == QPS_LINSYS_CG && cg_explicit) ? 1 : 0;
-            info->polishFlag = pr.flag; info->polishIterations = pr.minresIterations; info->tPolish = pr.seconds;
-        }
-    }
-    void get_dual(double* zh, double* yh) override {
-        HIPC(hipSetDevice(device));
-        if (zh) download_vec(z, zh, m);
-        if (yh) download_vec(y, yh, m);
-    }
-    // SolveQuadraticProgram.m:289-325 with the products of K as SpMVs (x block of length n, multiplier block of length m)
-    void polish_device(const qps_params& p, PolishReport* pr) {
-        PolishProduct<T> kmat = [&](const T* v, T delta, T* out, const T* mask, T* scratch) {
-            spmv(P, v, out, T(1), v, delta, nullptr, T(0), nullptr);                                // P v_x + delta v_x
-            if (m <= 0) return;
-            spmv(A, v, out + n, T(1), nullptr, T(0), nullptr, T(0), nullptr);                       // A v_x
-            polish_mask_rows<T>(st, (int)m, mask, v + n, delta, out + n, scratch);                  // mask . - delta mask v_lambda; scratch = mask v_lambda
-            spmv(At, scratch, out, T(1), out, T(1), nullptr, T(0), nullptr);                        // + A'(mask v_lambda)
-        };
-        polish_with<T>(st, n, m, (int)n, (int)m, q, l, u, y, x, p, pr, kmat);
-    }
-    void polish(double* xh, const double* yh, const qps_params& p, qps_polish_report* rep) override {
-        HIPC(hipSetDevice(device));
-        upload_vec(xh, x, n); upload_vec(yh, y, m);
-        PolishReport pr;
-        polish_device(p, &pr);
-        download_vec(x, xh, n);
-        if (rep) {
-            rep->flag = pr.flag; rep->refinements = pr.refinements; rep->minresIterations = pr.minresIterations;
-            rep->numActiveLower = pr.numLower; rep->numActiveUpper = pr.numUpper; rep->reserved0 = 0; rep->relres = pr.relres; rep->seconds = pr.seconds;
-        }
-    }
-    // qps_operator_apply: one application of P / A / A' / [P; A] / the reduced operator (LinearSystemSolvers.jl:152-157) through the SpMV kernels the loop
-    // uses for them; work buffers only (cu, cc: n; w, tm: m), the solver state stays
-    void operator_apply(int op, const double* in, double* out, double rho, double sigma) override {
-        HIPC(hipSetDevice(device));
-        if (op == QPS_OP_AT) {
-            upload_vec(in, w, m);
-            if (m > 0) spmv(At, w, cc, T(1), nullptr, T(0), nullptr, T(0), nullptr); else HIPC(hipMemsetAsync(cc, 0, sizeof(T) * (size_t)(n + 64), st));
-            download_vec(cc, out, n);
-            return;
-        }
-        upload_vec(in, cu, n);
-        if (op == QPS_OP_P) { spmv(P, cu, cc, T(1), nullptr, T(0), nullptr, T(0), nullptr); download_vec(cc, out, n); }
-        else if (op == QPS_OP_A) { if (m > 0) spmv(A, cu, tm, T(1), nullptr, T(0), nullptr, T(0), nullptr); download_vec(tm, out, m); }
-        else if (op == QPS_OP_PA) {
-            if (PA.blocked) {                                                                       // the stacked product of a CG iteration, then its blocks added up
-                spmv_blk(PA, cu, nullptr);
-                DeviceOwner tmp_mem;
-                T* both = tmp_mem.dalloc<T>(n + m + 64, st);
-                hipLaunchKernelGGL((k_spmv_combine<T>), dim3((unsigned)((n + m + 255) / 256)), dim3(256), 0, st, (int)(n + m), static_cast<const T*>(PA.partial), PA.nblk, (int64_t)(n + m),
-                                   T(1), (const T*)nullptr, 0, (int64_t)0, T(0), (const T*)nullptr, T(0), (const T*)nullptr, T(0), both, (const T*)nullptr, (double*)nullptr, (const CgState*)nullptr);
-                download_vec(both, out, n); download_vec(both + n, out + n, m);
-            } else {
-                spmv(P, cu, cc, T(1), nullptr, T(0), nullptr, T(0), nullptr); download_vec(cc, out, n);
-                if (m > 0) spmv(A, cu, tm, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                download_vec(tm, out + n, m);
-            }
-        } else if (op == QPS_OP_REDUCED) { op_reduced(cu, cc, rho, sigma, nullptr, nullptr); download_vec(cc, out, n); }
-        else throw QpsError(QPS_ERR_BAD_ARGUMENT, "unknown qps_operator_kind");
-    }
-    void linsys_set_cg(double eps, int itr) override { eps_pcg = eps; itr_pcg = itr; }             // LinOpCg!(...; ϵPcg, numItrPcg): LinearSystemSolvers.jl:164
-    void linsys_init(double rho, double sigma, int linsys, int) override {
-        HIPC(hipSetDevice(device));
-        if (linsys != QPS_LINSYS_AUTO && linsys != QPS_LINSYS_CG && linsys != QPS_LINSYS_KKT_LDL && linsys != QPS_LINSYS_CG_EXPLICIT)
-            throw QpsError(QPS_ERR_UNSUPPORTED, "CSR handles offer QPS_LINSYS_CG, QPS_LINSYS_CG_EXPLICIT and QPS_LINSYS_KKT_LDL (create with dense_path=1 for the reduced Cholesky path)");
-        plugin_kind = resolve_kind(linsys, rho, sigma, true);                                       // LinearSystemSolvers.jl:18 / :49 / :81
-        if (plugin_kind == QPS_LINSYS_KKT_LDL) return;
-        HIPC(hipMemsetAsync(xx, 0, sizeof(T) * (size_t)(n + 64), st));                              // LinOpCgInit (:147)
-        cg_total = 0; last_cg = 4;
-    }
-    void linsys_solve(const double* xh, const double* zh, const double* yh, double rho, double sigma, int changed, double* xxh, double* zzh) override {
-        HIPC(hipSetDevice(device));
-        if (plugin_kind == QPS_LINSYS_KKT_LDL) {
-            if (!ldl) throw QpsError(QPS_ERR_BAD_ARGUMENT, "qps_linsys_solve called before qps_linsys_init");
-            if (changed) ldl_prepare(rho, sigma, true);                                             // :30-32 / :61-63 / :93-95
-        }
-        if (plugin_kind == QPS_LINSYS_CG && cg_explicit) reduced_values(rho, sigma);                 // :127-129 (a no-op while rho and sigma are the cached ones)
-        upload_vec(xh, x, n); upload_vec(zh, z, m); upload_vec(yh, y, m);
-        linear_solve(rho, sigma);
-        HIPC(hipStreamSynchronize(st));
-        download_vec(xx, xxh, n); download_vec(zz, zzh, m);
-    }
-};
-
-
-// =================================================================================================================
-// SparseProxQP (ProxQP.jl:71, :95-115; sparse branches :184-190, :201-206, :335-372): the second solver form on SparseMatrixCSC inputs.
-//
-// The reference keeps M = P + rho (A'A + C'C) + sigma I as a sparse matrix with a frozen pattern (AlignSparsePattern :351-372, diagonal
-// positions :335-349), rewrites its values on a rho update (UpdateM! :184-190) and re-factorises with the pattern-reusing `cholesky!`
-// (:201-206).  Here the same linear system is solved in its KKT form
-//     [P + sigma I   G' ; G   -I / rho] [x ; nu] = [sigma x - q ; h - dual / rho],     G = [A; C],  h = [b ; d - s],  dual = [y ; z]
-// (eliminating nu gives exactly M x = sigma x - q + G'[rho b - y ; rho (d - s) - z], CalculateRhs! :208-219) with the sparse L D L' plugin
-// of the main path: ordering + symbolic factor once per handle, a rho update is numeric only -- the pattern-reusing re-factorisation --
-// and G x, which the row updates (:227-249) need, comes back with the solve (z~ = z + (nu - y) / rho = G x).  G'G is never formed: the
-// reduced matrix of a sparse G is much denser than [.. G'; G ..].  CheckConvergence! (:252-298) runs on the CSR SpMVs of the main path.
-// The six-argument constructor's start (:95-115: [P A'; A 0] [x; y] = [-q; b]) uses a second factor, of [P A'; A -delta I], and iterative
-// refinement against the unperturbed system.
-// =================================================================================================================
-template <typename T> struct SparseProxQpSolver : ProxQpBase {
-    std::unique_ptr<SparseSolver<T>> ss;          // P, G = [A; C] as CSR (G, G'), the L D L' plugin, the staging buffers; owns the stream
-    DeviceOwner mem; hipStream_t st = nullptr;    // this solver's own buffers: gone before `ss` and its stream lease
-    int mtot = 0;
-    T *g = nullptr, *dual = nullptr, *slack = nullptr, *hvec = nullptr, *x = nullptr, *xx = nullptr, *v = nullptr, *de = nullptr, *di = nullptr;
-    T *X1 = nullptr, *X2 = nullptr, *X3 = nullptr, *r1 = nullptr, *r2 = nullptr, *dx = nullptr, *dnu = nullptr, *zero_m = nullptr;
-    unsigned long long* slots = nullptr; unsigned long long* slots_host = nullptr;
-    // canonical 0-based host copies of P and A for the factor of the initialisation (dropped after init_kkt / set_state)
-    std::vector<int64_t> kPcp, kPri, kAcp, kAri; std::vector<double> kPnz, kAnz;
-
-    static dim3 g1(int64_t c) { return dim3((unsigned)((std::max<int64_t>(c, 1) + 255) / 256)); }
-
-    SparseProxQpSolver(int dev, int64_t n_, int64_t me_, int64_t mi_, int dt, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const double* qh,
-                       const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* bh, const int64_t* Ccp, const int64_t* Cri, const double* Cnz,
-                       const double* dh, int base) {
-        device = dev; n = n_; me = me_; mi = mi_; mtot = (int)(me + mi);
-        // G = [A; C] column by column (rows of C shifted by numEq), 0-based; P re-based
-        std::vector<int64_t> Gcp(n + 1, 0), Gri, P0cp(n + 1), P0ri((size_t)(Pcp[n] - base));
-        std::vector<double> Gnz;
-        for (int64_t j = 0; j <= n; ++j) P0cp[j] = Pcp[j] - base;
-        for (size_t k = 0; k < P0ri.size(); ++k) P0ri[k] = Pri[k] - base;
-        for (int64_t j = 0; j < n; ++j) {
-            if (me > 0) for (int64_t k = Acp[j] - base; k < Acp[j + 1] - base; ++k) { Gri.push_back(Ari[k] - base); Gnz.push_back(Anz[k]); }
-            if (mi > 0) for (int64_t k = Ccp[j] - base; k < Ccp[j + 1] - base; ++k) { Gri.push_back(Cri[k] - base + me); Gnz.push_back(Cnz[k]); }
-            Gcp[j + 1] = (int64_t)Gri.size();
-        }
-        std::vector<double> zeros((size_t)std::max(mtot, 1), 0.0), gh((size_t)std::max(mtot, 1), 0.0);
-        for (int64_t i = 0; i < me; ++i) gh[i] = bh[i];
-        for (int64_t i = 0; i < mi; ++i) gh[me + i] = dh[i];
-        static const int64_t dummy_i[1] = {0}; static const double dummy_d[1] = {0.0};
-        ss.reset(new SparseSolver<T>(dev, n, mtot, dt, P0cp.data(), P0ri.empty() ? dummy_i : P0ri.data(), Pnz, Gcp.data(), Gri.empty() ? dummy_i : Gri.data(),
-                                     Gnz.empty() ? dummy_d : Gnz.data(), qh, zeros.data(), zeros.data(), 0));
-        st = ss->st;
-        const int64_t nn = n + 64, mm = mtot + 64;
-        g = mem.dalloc<T>(mm, st); dual = mem.dalloc<T>(mm, st); slack = mem.dalloc<T>(mm, st); hvec = mem.dalloc<T>(mm, st); v = mem.dalloc<T>(mm, st); de = mem.dalloc<T>(mm, st); di = mem.dalloc<T>(mm, st);
-        r2 = mem.dalloc<T>(mm, st); dnu = mem.dalloc<T>(mm, st); zero_m = mem.dalloc<T>(mm, st);
-        x = mem.dalloc<T>(nn, st); xx = mem.dalloc<T>(nn, st); X1 = mem.dalloc<T>(nn, st); X2 = mem.dalloc<T>(nn, st); X3 = mem.dalloc<T>(nn, st); r1 = mem.dalloc<T>(nn, st); dx = mem.dalloc<T>(nn, st);
-        slots = mem.dalloc<unsigned long long>(16, st);
-        slots_host = reinterpret_cast<unsigned long long*>(ss->lease.res.pinned);
-        ss->upload_vec(gh.data(), g, mtot);
-        layout::canonical_csc(n, P0cp.data(), P0ri.empty() ? dummy_i : P0ri.data(), Pnz, 0, kPcp, kPri, kPnz);
-        if (me > 0) layout::canonical_csc(n, Acp, Ari, Anz, base, kAcp, kAri, kAnz);
-        else kAcp.assign(n + 1, 0);
-    }
-    ~SparseProxQpSolver() override {
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(st);
-    }
-    void drop_init_copies() {
-        for (auto* vv : {&kPcp, &kPri, &kAcp, &kAri}) std::vector<int64_t>().swap(*vv);
-        std::vector<double>().swap(kPnz); std::vector<double>().swap(kAnz);
-    }
-    void set_state(const double* xh, const double* yh, const double* zh, const double* sh) override {
-        HIPC(hipSetDevice(device));
-        ss->upload_vec(xh, x, n); ss->upload_vec(yh, dual, me); ss->upload_vec(zh, dual + me, mi);
-        HIPC(hipMemsetAsync(slack, 0, sizeof(T) * (size_t)(mtot + 64), st));
-        ss->upload_vec(sh, slack + me, mi);
-    }
-    void get_state(double* xh, double* yh, double* zh, double* sh) override {
-        HIPC(hipSetDevice(device));
-        if (xh) ss->download_vec(x, xh, n);
-        if (yh) ss->download_vec(dual, yh, me);
-        if (zh) ss->download_vec(dual + me, zh, mi);
-        if (sh) ss->download_vec(slack + me, sh, mi);
-    }
-    void axpby(int64_t c, T a, const T* xa, T b, const T* ya, T* out) { if (c > 0) hipLaunchKernelGGL((k_axpby<T>), g1(c), dim3(256), 0, st, (int)c, a, xa, b, ya, out); }
-
-    // ProxQP.jl:95-115: [P A'; A 0] [x; y] = [-q; b], s = max(d - C x, 0), z = 0
-    void init_kkt() override {
-        HIPC(hipSetDevice(device));
-        if (kPcp.empty()) throw QpsError(QPS_ERR_BAD_ARGUMENT, "qps_proxqp_init_kkt: the initialisation data of this handle was released (call it once, before set_state)");
-        const double delta = sizeof(T) == 8 ? 1e-8 : 1e-3;
-        LdlSymbolic sym;
-        try { sym = ldl_analyze((int)n, (int)me, kPcp.data(), kPri.data(), kAcp.data(), kAri.data(), 0, 8192, 64, 4096); }
-        catch (const std::runtime_error& e) { throw QpsError(QPS_ERR_UNSUPPORTED, e.what()); }
-        std::unique_ptr<SparseLdl<T>> kkt = make_sparse_ldl<T>(st, std::move(sym), kPnz.data(), (int64_t)kPnz.size(), kAnz.data(), (int64_t)kAnz.size());
-        // [P + delta I, A'; A, -delta I]: quasi-definite for every positive SEMI-definite P, so a singular P with a non-singular KKT matrix -- which the
-        // reference's `mK \\ vR` (an LU, ProxQP.jl:103-106) accepts -- factorises too; the refinement below runs against the UNSHIFTED system
-        kkt->factorize(1.0 / delta, delta);
-        HIPC(hipMemsetAsync(x, 0, sizeof(T) * (size_t)(n + 64), st));
-        HIPC(hipMemsetAsync(dual, 0, sizeof(T) * (size_t)(mtot + 64), st));
-        HIPC(hipMemsetAsync(de, 0, sizeof(T) * (size_t)(mtot + 64), st));
-        // Iterative refinement against the UNSHIFTED system until the residual stops falling (at most 50 steps).  In the directions of P that A does not pin
-        // a step contracts the error only by delta / (lambda + delta): with fp32's delta = 1e-3 and lambda_min(P) = 5e-4 that is 0.67 per step, which a fixed
-        // count of 7 left at 6e-2 and the handle was refused although the reference's `mK \ vR` (ProxQP.jl:103-106) solves the system.  The start need not be
-        // exact (ProxQP iterates from it): it is refused only when the residual stops falling above the tolerance -- a singular [P A'; A 0], on which the reference's
-        // backslash fails as well: the inconsistent part of the right-hand side stays while |x| grows by ~1 / delta per step -- or turns non-finite.
-        std::vector<double> hr((size_t)n), hq((size_t)n), hr2((size_t)std::max<int64_t>(me, 1), 0.0), hb((size_t)std::max<int64_t>(me, 1), 0.0);
-        auto amax = [](const std::vector<double>& a_) { double m_ = 0; for (double t : a_) { if (std::isnan(t)) return (double)INFINITY; m_ = std::fmax(m_, std::fabs(t)); } return m_; };
-        ss->download_vec(ss->q, hq.data(), n);
-        if (me > 0) ss->download_vec(g, hb.data(), me);
-        // against the right-hand side ONLY: a singular system answers the shifted solve with |x| ~ 1 / delta, and a scale that included |x| would
-        // normalise the residual it leaves behind away
-        const double scale = std::fmax(1.0, std::fmax(amax(hq), amax(hb)));
-        const double target = sizeof(T) == 8 ? 1e-12 : 1e-6;
-        double res0 = INFINITY, best = INFINITY, res = INFINITY; int stalled = 0;
-        for (int it = 0; it <= 50; ++it) {
-            // residual of the UNPERTURBED system: r1 = -q - P x - A'y, r2 = b - A x (the rows of C carry zeros in `de`, so G'de = A'y)
-            ss->spmv(ss->P, x, r1, T(-1), ss->q, T(-1), nullptr, T(0), nullptr);
-            if (me > 0) {
-                HIPC(hipMemcpyAsync(de, dual, sizeof(T) * (size_t)me, hipMemcpyDeviceToDevice, st));
-                ss->spmv(ss->At, de, r1, T(-1), r1, T(1), nullptr, T(0), nullptr);
-                ss->spmv(ss->A, x, v, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                axpby(me, T(1), g, T(-1), v, r2);
-            }
-            ss->download_vec(r1, hr.data(), n);
-            if (me > 0) ss->download_vec(r2, hr2.data(), me);
-            res = std::fmax(amax(hr), amax(hr2)) / scale;
-            if (it == 0) res0 = res;
-            if (!std::isfinite(res)) break;
-            if (res <= target || it == 50) break;
-            if (res < 0.99 * best) stalled = 0; else if (++stalled >= 3) break;  // three steps without a 1 % gain: as good as this factor gets
-            best = std::fmin(best, res);
-            kkt->solve_raw(r1, r2, dx, dnu);
-            axpby(n, T(1), x, T(1), dx, x);
-            axpby(me, T(1), dual, T(1), dnu, dual);
-        }
-        {
-            const double accept = sizeof(T) == 8 ? 1e-6 : 1e-2;
-            // refused: non-finite, or a residual that has stopped falling ABOVE the tolerance -- the floor an inconsistent (singular) system leaves, |r| = the part of
-            // [-q; b] outside the range; a residual that is still falling after 50 steps is an approximate start, and a start is all ProxQP needs
-            if (!std::isfinite(res) || (res > accept && stalled >= 3)) {
-                char bmsg[320]; snprintf(bmsg, sizeof bmsg, "qps_proxqp_init_kkt: the iterative refinement of [P A'; A 0] [x; y] = [-q; b] did not converge (relative residual %.3g after starting at %.3g): "
-                                                          "the KKT matrix is singular or too ill-conditioned", res, res0);
-                throw QpsError(QPS_ERR_FACTORIZATION, bmsg);
-            }
-        }
-        if (mtot > 0) {
-            ss->spmv(ss->A, x, v, T(1), nullptr, T(0), nullptr, T(0), nullptr);                    // G x
-            hipLaunchKernelGGL((pqrows::k_pq_init_s<T>), g1(mtot), dim3(256), 0, st, (int)me, mtot, g, v, dual, slack);   // :110-111
-        }
-        HIPC(hipStreamSynchronize(st));
-        drop_init_copies();
-    }
-
-    void solve(const qps_proxqp_params& p, qps_proxqp_report* rep) override {
-        HIPC(hipSetDevice(device));
-        drop_init_copies();
-        double rho = p.rho; const double sigma = p.sigma;
-        int converged = 0, conv_it = p.numIterations; double resP = INFINITY, resD = INFINITY, rho_rep = p.rho;
-        ss->ldl_prepare(rho, sigma, true);                                                          // UpdateDecomposition! (ProxQP.jl:131, :201-206)
-        const char* gxs = getenv("QPS_PROXQP_GX_SOLVE");                                            // read per solve
-        const bool gx_product = !(gxs && gxs[0] == '1');
-        for (int ii = 1; ii <= p.numIterations; ++ii) {                                             // :135
-            const bool check = (ii % p.numItrConv == 0);
-            if (mtot > 0) hipLaunchKernelGGL((pqrows::k_pq_h<T>), g1(mtot), dim3(256), 0, st, (int)me, mtot, g, slack, hvec);
-            ss->ldl->solve(x, ss->q, hvec, dual, rho, sigma, xx, v);                                // CalculateRhs! + UpdateX! (:208-225)
-            std::swap(x, xx);
-            // `mA * vX`, `mC * vX` of the row updates (:230-248) by the product itself, as the reference forms them -- not the G x that falls out of the KKT solve
-            // (same value up to the un-refined, un-pivoted solve's error).  The reference's check (:264-266) repeats the SAME product, so `C x - d + s` with
-            // s = d - C x cancels EXACTLY on rows with z = 0; a primal residual of exactly 0 sends rho to its lower clamp (:281-283), a residual of 1e-16 to
-            // rho * 1e-4: with G x from the solve in the updates and from the product in the check the two runs part for good (ProxQP fuzz, seed 43, case 184).
-            if (mtot > 0 && gx_product) ss->spmv(ss->A, x, v, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-            if (mtot > 0) hipLaunchKernelGGL((pqrows::k_pq_update<T>), g1(mtot), dim3(256), 0, st, (int)me, mtot, g, v, dual, slack, (T)rho);   // :227-249
-            if (check) {                                                                            // :151  CheckConvergence! :252-298
-                ss->spmv(ss->P, x, X1, T(1), nullptr, T(0), nullptr, T(0), nullptr);                // :261
-                HIPC(hipMemsetAsync(X2, 0, sizeof(T) * (size_t)n, st)); HIPC(hipMemsetAsync(X3, 0, sizeof(T) * (size_t)n, st));
-                if (mtot > 0) {
-                    hipLaunchKernelGGL((pqrows::k_pq_split<T>), g1(mtot), dim3(256), 0, st, (int)me, mtot, dual, de, di);
-                    ss->spmv(ss->At, de, X2, T(1), nullptr, T(0), nullptr, T(0), nullptr);          // A'y (:262)
-                    ss->spmv(ss->At, di, X3, T(1), nullptr, T(0), nullptr, T(0), nullptr);          // C'z (:263)
-                }
-                // mA * vX, mC * vX of CheckConvergence! (:264-265): the product the row updates have just used (QPS_PROXQP_GX_SOLVE=1: recomputed here -- the
-                // solve's G x carries the error of the un-refined L D L' solve, which must not go into the reported primal residual)
-                if (mtot > 0 && !gx_product) ss->spmv(ss->A, x, v, T(1), nullptr, T(0), nullptr, T(0), nullptr);
-                HIPC(hipMemsetAsync(slots, 0, 16 * sizeof(unsigned long long), st));
-                hipLaunchKernelGGL((pqrows::k_pq_norms<T>), dim3(64), dim3(256), 0, st, (int)n, (int)me, mtot, v, g, slack, X1, X2, X3, ss->q, slots);
-                HIPC(hipMemcpyAsync(slots_host, slots, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                HIPC(hipStreamSynchronize(st));
-                const pqrows::CheckOutcome co = pqrows::decide(slots_host, p, rho);                 // :266-294
-                rho = co.rho; converged = co.converged ? 1 : 0; resP = co.resPrim; resD = co.resDual;
-                if (converged) conv_it = ii;                                                        // :155-157 (no break)
-                if (co.updated) { ss->ldl_prepare(rho, sigma, true); rho_rep = rho; }               // :159-165: UpdateM! + pattern-reusing cholesky!
-            }
-        }
-        HIPC(hipStreamSynchronize(st));
-        if (rep) { rep->converged = converged; rep->iterations = conv_it; rep->rho = rho_rep; rep->sigma = sigma; rep->resPrim = resP; rep->resDual = resD; }
-    }
-};
+}
+int dot_parts(const Csr& M) { return M.blocked ? (M.nrows + 255) / 256 : M.nblocks; }
 
 }  // namespace
 
-ProxQpBase* make_proxqp_sparse(int device, int64_t n, int64_t me, int64_t mi, int dtype, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const double* q,
-                               const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* b, const int64_t* Ccp, const int64_t* Cri, const double* Cnz,
-                               const double* d, int index_base) {
-    if (dtype == QPS_F64) return new SparseProxQpSolver<double>(device, n, me, mi, dtype, Pcp, Pri, Pnz, q, Acp, Ari, Anz, b, Ccp, Cri, Cnz, d, index_base);
-    return new SparseProxQpSolver<float>(device, n, me, mi, dtype, Pcp, Pri, Pnz, q, Acp, Ari, Anz, b, Ccp, Cri, Cnz, d, index_base);
+// ---- SparseMatrices ------------------------------------------------------------------------------------------------------------------------------------------
+template <typename T> SparseMatrices<T>::SparseMatrices(int device_, int64_t n_, int64_t m_) : device(device_), n(n_), m(m_) {
+    HIPC(hipSetDevice(device));
+    st = lease.acquire(device);   // recycled stream + pinned block (qps_internal.h)
+    up.reset(new StagedUploader(st));
+    stage = mem.dalloc<double>(std::max(n + 64, m + 64) + 64, st);
+}
+template <typename T> void SparseMatrices<T>::load(const layout::CsrHost& Ph, const layout::CsrHost& Ah, const layout::CsrHost& Ath) {
+    upload_csr(P, Ph);
+    upload_csr(At, Ath);
+    upload_csr(A, Ah);
+}
+// Column-blocked copy of M: the sliced form (k_spmv_sell) when the host builder produces one, else the task form (k_spmv_blk).  The layouts are
+// built by plain host code (spmv_layout.cpp, tested on the CPU against scipy); here they are only uploaded.
+template <typename T> void SparseMatrices<T>::build_blocked(Csr& M, const layout::CsrHost& H, bool with_src) {
+    static const int wgs_env = [] { const char* e = getenv("QPS_SPMV_WGS"); return e ? atoi(e) : 0; }();
+    const int wgs = wgs_env > 0 ? wgs_env : 512;
+    M.ncols = H.ncols;
+    const char* e = getenv("QPS_SPMV_SELL");                     // read per handle: 0 = the task form (k_spmv_blk)
+    if (!(e && atoi(e) == 0)) {
+        layout::SellLayout<T> L;
+        const char* es = getenv("QPS_SPMV_STAGED");                 // read per handle: 0 = row sums stored lane by lane also when whole windows could be staged
+        if (layout::build_sell<T>(H, wgs, L, with_src, !(es && atoi(es) == 0))) {
+            M.nblk = L.nblk; M.nsl = L.nsl; M.wpb = L.wpb; M.win = L.win; M.nwin = L.nwin; M.staged = L.staged;
+            if (with_src) { M.src = upload_array(L.src); M.src_n = (int64_t)L.src.size(); M.lsrc = upload_array(L.lsrc); M.lsrc_n = (int64_t)L.lsrc.size(); }
+            M.s_cols = upload_array(L.cols); M.s_vals = upload_array(L.vals);
+            M.bci = upload_array(L.lci); M.bva = upload_array(L.lva);
+            M.sl_off = upload_array(L.sl_off); M.sl_perm = upload_array(L.perm); M.wg_ptr = upload_array(L.wg_ptr);
+            M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
+            M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);
+            M.blocked = true; M.sell = true;
+            return;
+        }
+    }
+    layout::TaskLayout<T> L;
+    try { layout::build_tasks<T>(H, wgs, L, with_src); }
+    catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
+    M.nblk = L.nblk; M.wpb = L.wpb; M.per = L.per; M.lpr4 = L.lpr4;
+    if (with_src) { M.src = upload_array(L.src); M.src_n = (int64_t)L.src.size(); }
+    M.brp = upload_array(L.brp); M.bci = upload_array(L.bci); M.bva = upload_array(L.bva);
+    M.task_ptr = upload_array(L.task_ptr); M.tasks = reinterpret_cast<int4*>(upload_array(L.tasks));
+    M.lr_ptr = upload_array(L.lr_ptr); M.lr_desc = reinterpret_cast<int4*>(upload_array(L.lr));
+    M.partial = mem.dalloc<T>((int64_t)L.nblk * H.nrows + 64, st);    // + 64: the dump slots of lanes without a row
+    M.blocked = true;
+}
+template <typename T> void SparseMatrices<T>::upload_csr(Csr& M, const layout::CsrHost& H, bool with_src) {
+    M.nrows = H.nrows; M.nnz = (int64_t)H.ci.size();
+    {   // LDS-resident x pays once the gathers dominate; QPS_SPMV_BLOCKED = 1 / 0 forces the choice
+        // ... and only while the per-block partial sums (one per row and column block, written by the product and read back by its combine launch) stay below
+        // the matrix itself: a long banded matrix (n = 400 000: 56 column blocks) has 2.7 partial sums per entry -- 165 us per product where the CSR-stream
+        // kernel, whose gathers of x stay inside the band and hit the cache, needs a third of that
+        const char* e = getenv("QPS_SPMV_BLOCKED");
+        const int64_t nblk_ = (H.ncols + BlkOf<T>::CB - 1) / BlkOf<T>::CB;
+        const bool want = e ? atoi(e) != 0 : (M.nnz >= 200000 && nblk_ * (int64_t)H.nrows <= M.nnz);
+        if (want && H.nrows > 0 && H.ncols > 0) build_blocked(M, H, with_src);
+    }
+    M.rp = upload_array(H.rp); M.ci = upload_array(H.ci);
+    {
+        std::vector<T> v(H.va.begin(), H.va.end());
+        M.va = upload_array(v);
+    }
+    const std::vector<int> rbv = layout::stream_row_blocks(H);   // row blocks of the CSR-stream kernel
+    M.nblocks = (int)rbv.size() - 1;
+    M.rb = upload_array(rbv);
+}
+template <typename T> void SparseMatrices<T>::mul(const Csr& M, const T* xin, T* out, const SpmvEpilogue<T>& e) {
+    if (M.nblocks <= 0) return;
+    if (M.blocked) {
+        spmv_blk(st, M, xin, e.stt);
+        hipLaunchKernelGGL((k_spmv_combine<T>), dim3((M.nrows + 255) / 256), dim3(256), 0, st, M.nrows, static_cast<const T*>(M.partial), M.nblk, (int64_t)M.nrows, e.a,
+                           (const T*)nullptr, 0, (int64_t)0, T(0), e.add0, e.b0, e.add1, e.b1, out, e.dotv, e.partial, e.stt);
+        return;
+    }
+    hipLaunchKernelGGL((k_spmv_stream<T>), dim3(M.nblocks), dim3(256), 0, st, M.rb, M.rp, M.ci, static_cast<const T*>(M.va), xin, out, e.a,
+                       e.add0, e.b0, e.add1, e.b1, e.dotv, e.partial, e.stt);
+}
+template <typename T> void SparseMatrices<T>::axpby(int64_t count, T a, const T* x, T b, const T* y, T* out) {
+    if (count > 0) hipLaunchKernelGGL((k_axpby<T>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (int)count, a, x, b, y, out);
 }
 
-SolverBase* make_sparse_solver(int device, int64_t n, int64_t m, int dtype, const int64_t* Pcp, const int64_t* Pri,
-                               const double* Pnz, const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* q,
-                               const double* l, const double* u, int index_base) {
-    if (dtype == QPS_F64) return new SparseSolver<double>(device, n, m, dtype, Pcp, Pri, Pnz, Acp, Ari, Anz, q, l, u, index_base);
-    return new SparseSolver<float>(device, n, m, dtype, Pcp, Pri, Pnz, Acp, Ari, Anz, q, l, u, index_base);
+// ---- CgPlugin ------------------------------------------------------------------------------------------------------------------------------------------------
+template <typename T> void CgPlugin<T>::build(const layout::CsrHost& Ph, const layout::CsrHost& Ah) {
+    const int64_t n = M.n, m = M.m, pnnz = (int64_t)Ph.ci.size(), annz = (int64_t)Ah.ci.size();
+    hipStream_t st = M.st;
+    const char* fuse_env = getenv("QPS_SPMV_FUSEPA");                 // 0: keep P, A, A' as three separate blocked products
+    if (m > 0 && M.P.blocked && M.A.blocked && M.At.blocked && pnnz + annz < 2000000000LL && !(fuse_env && atoi(fuse_env) == 0)) {
+        const layout::CsrHost Sh = layout::stack_rows(Ph, Ah);
+        PA.nrows = (int)(n + m); PA.nnz = pnnz + annz;
+        M.build_blocked(PA, Sh);
+    }
+    const int64_t nn = n + 64, mm = m + 64;
+    cu = M.mem.template dalloc<T>(nn, st); cu2 = M.mem.template dalloc<T>(nn, st); cr = M.mem.template dalloc<T>(nn, st); cc = M.mem.template dalloc<T>(nn, st);
+    tm = M.mem.template dalloc<T>(mm, st);
+    nb_n = (int)((n + 255) / 256);
+    part_uc_cap = std::max(std::max(M.At.nblocks, M.P.nblocks), nb_n + (int)((m + 255) / 256)) + 64;
+    part_uc = M.mem.template dalloc<double>(part_uc_cap, st); part_rr = M.mem.template dalloc<double>(nb_n + 64, st);
+    state = reinterpret_cast<CgState*>(M.mem.template dalloc<double>(16, st));
 }
+// ItrSolCgInit (LinearSystemSolvers.jl:110-122): mAA = mA' * mA, mPI = mP + sigma I, mL = mPI + rho * mAA, formed on the host ONCE per handle as three value
+// arrays on the frozen pattern of mL (spmv_layout.cpp: reduced_matrix); returns whether the handle has it.  forced = an explicit QPS_LINSYS_CG_EXPLICIT request;
+// otherwise the matrix is only formed when it pays -- A'A cheap to form (sum of squared row lengths) and mL no larger than 1.5 x the entries the matrix-free
+// operator streams per application (nnz P + 2 nnz A).  BASELINE config 3 (unstructured, ~50 entries per row) fails the first test in O(m) and stays matrix-free.
+template <typename T> bool CgPlugin<T>::explicit_prepare(bool forced, const KktPlugin<T>& kkt) {
+    if (L.state != 0) {
+        if (forced && L.state < 0) throw QpsError(QPS_ERR_UNSUPPORTED, "QPS_LINSYS_CG_EXPLICIT: the reduced matrix of this handle cannot be formed (too many entries, or the handle's "
+                                                                              "host copies were released to the direct plugin before the first CG request)");
+        return L.state > 0;
+    }
+    L.state = -1;
+    if (kkt.released()) { if (forced) return explicit_prepare(true, kkt); return false; }   // released (the L D L' plugin was built first)
+    const KktHostCsc& h = kkt.host;
+    const int64_t n = M.n, m = M.m, pnnz = (int64_t)h.Pri.size(), annz = (int64_t)h.Ari.size();
+    layout::CsrHost Ph, Ah, Ath, Lh; std::vector<double> vAA, dg;
+    try {
+        Ph = layout::csc_as_transposed_csr(n, n, h.Pcp, h.Pri, h.Pnz);
+        layout::csc_to_csr_pair(m, n, h.Acp, h.Ari, h.Anz, Ah, Ath);
+        if (!forced && layout::ata_work(Ah) > 16 * (pnnz + annz)) return false;
+        const int64_t cap = forced ? 1900000000LL : (3 * (pnnz + 2 * annz)) / 2 + n;
+        if (!layout::reduced_matrix(Ph, Ah, Ath, cap, Lh, vAA, dg)) { if (forced) return explicit_prepare(true, kkt); return false; }
+    } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
+    M.up.reset(new StagedUploader(M.st));
+    M.upload_csr(L.mat, Lh, true);
+    std::vector<T> t1(Lh.va.begin(), Lh.va.end()), t2(vAA.begin(), vAA.end()), t3(dg.begin(), dg.end());
+    L.vP = M.upload_array(t1); L.vAA = M.upload_array(t2); L.dg = M.upload_array(t3);
+    M.up.reset();
+    HIPC(hipStreamSynchronize(M.st));
+    if (dot_parts(L.mat) + 64 > part_uc_cap) {                                                     // partials of dot(u, mL u): one per workgroup of the product's last launch
+        M.mem.release(part_uc); part_uc = nullptr;
+        part_uc_cap = dot_parts(L.mat) + 64; part_uc = M.mem.template dalloc<double>(part_uc_cap, M.st);
+    }
+    L.state = 1; L.valid = false;
+    return true;
+}
+// the values of mL for (rho, sigma): LinearSystemSolvers.jl:114 at Init, :127-129 on changedRho -- elementwise on the frozen pattern, then the column-blocked copy refreshed
+template <typename T> void CgPlugin<T>::reduced_values(double rho, double sigma) {
+    if (L.valid && L.rho == rho && L.sigma == sigma) return;
+    hipStream_t st = M.st;
+    const int64_t nnz = L.mat.nnz;
+    if (nnz > 0) hipLaunchKernelGGL((k_build_reduced<T>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, L.vP, L.vAA, L.dg, (T)sigma, (T)rho, static_cast<T*>(L.mat.va));
+    if (L.mat.blocked) {
+        T* main_vals = static_cast<T*>(L.mat.sell ? L.mat.s_vals : L.mat.bva);
+        if (L.mat.src_n > 0) hipLaunchKernelGGL((k_refresh_values<T>), dim3((unsigned)((L.mat.src_n + 255) / 256)), dim3(256), 0, st, L.mat.src_n, L.mat.src, static_cast<const T*>(L.mat.va), main_vals);
+        if (L.mat.sell && L.mat.lsrc_n > 0)
+            hipLaunchKernelGGL((k_refresh_values<T>), dim3((unsigned)((L.mat.lsrc_n + 255) / 256)), dim3(256), 0, st, L.mat.lsrc_n, L.mat.lsrc, static_cast<const T*>(L.mat.va), static_cast<T*>(L.mat.bva));
+    }
+    L.valid = true; L.rho = rho; L.sigma = sigma;
+}
+// A CG request is served by the explicit reduced matrix (ItrSolCg, one product per CG iteration) when the handle has one -- always for
+// QPS_LINSYS_CG_EXPLICIT, for QPS_LINSYS_CG / AUTO when explicit_prepare finds that it pays (QPS_CG_EXPLICIT = 0 keeps those matrix-free) -- else by the
+// matrix-free operator (LinOpCg / LinMapsCg, three products).
+template <typename T> int CgPlugin<T>::resolve_cg(int linsys, double rho, double sigma, const KktPlugin<T>& kkt) {
+    const char* e = getenv("QPS_CG_EXPLICIT");                                                  // read per request
+    cg_explicit = linsys == QPS_LINSYS_CG_EXPLICIT ? explicit_prepare(true, kkt) : (!(e && atoi(e) == 0) && explicit_prepare(false, kkt));
+    if (cg_explicit) reduced_values(rho, sigma);
+    return QPS_LINSYS_CG;
+}
+// c = P u + rho A'(A u) + sigma u (LinearSystemSolvers.jl:152-157) as three streamed SpMVs; optional partials of dot(u, c)
+template <typename T> void CgPlugin<T>::op_reduced(const T* uin, T* cout, double rho, double sigma, double* partial, const CgState* stt) {
+    const int64_t n = M.n, m = M.m;
+    SpmvEpilogue<T> plain; plain.stt = stt;
+    if (m > 0 && M.P.blocked && M.A.blocked && M.At.blocked) {
+        // three blocked products; P u and A'(A u) share one combine launch that also forms the dot partials
+        spmv_blk(M.st, M.P, uin, stt);
+        M.mul(M.A, uin, tm, plain);
+        spmv_blk(M.st, M.At, tm, stt);
+        hipLaunchKernelGGL((k_spmv_combine<T>), dim3(nb_n), dim3(256), 0, M.st, (int)n, static_cast<const T*>(M.P.partial), M.P.nblk, (int64_t)n, T(1),
+                           static_cast<const T*>(M.At.partial), M.At.nblk, (int64_t)n, (T)rho, uin, (T)sigma, (const T*)nullptr, T(0), cout, partial ? uin : nullptr, partial, stt);
+        return;
+    }
+    SpmvEpilogue<T> pu; pu.add0 = uin; pu.b0 = (T)sigma; pu.stt = stt;                           // P u + sigma u; with no A this is c, and carries dot(u, c)
+    if (m <= 0) { pu.dotv = uin; pu.partial = partial; }
+    M.mul(M.P, uin, cout, pu);
+    if (m > 0) {
+        M.mul(M.A, uin, tm, plain);
+        SpmvEpilogue<T> at; at.a = (T)rho; at.add0 = cout; at.b0 = T(1); at.dotv = uin; at.partial = partial; at.stt = stt;   // c += rho A'(A u); dot(u, c)
+        M.mul(M.At, tm, cout, at);
+    }
+}
+template <typename T> void CgPlugin<T>::stacked_product(const T* uin, T* both) {
+    const int64_t nm = M.n + M.m;
+    spmv_blk(M.st, PA, uin, nullptr);
+    hipLaunchKernelGGL((k_spmv_combine<T>), dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, M.st, (int)nm, static_cast<const T*>(PA.partial), PA.nblk, (int64_t)nm,
+                       T(1), (const T*)nullptr, 0, (int64_t)0, T(0), (const T*)nullptr, T(0), (const T*)nullptr, T(0), both, (const T*)nullptr, (double*)nullptr, (const CgState*)nullptr);
+}
+
+// IterativeSolvers.cg!(xx, Op, tt; abstol = eps_pcg, maxiter = itr_pcg), xx warm started
+template <typename T> int CgPlugin<T>::cg(double rho, double sigma, const T* tt, T* xx) {
+    const int64_t n = M.n, m = M.m;
+    hipStream_t st = M.st;
+    const Csr& At = M.At;
+    CgState* const state_host = M.cg_state_host();
+    CgState* slot[2] = {state, state + 1};
+    int cur = 0;
+    // c = mL u: ONE product with the explicit matrix (ItrSolCg!, LinearSystemSolvers.jl:137) or the three of the matrix-free operator (:152-157)
+    auto apply_op = [&](const T* uin, T* cout, double* partial, const CgState* stt) {
+        if (cg_explicit) { SpmvEpilogue<T> e; e.dotv = partial ? uin : nullptr; e.partial = partial; e.stt = stt; M.mul(L.mat, uin, cout, e); }
+        else op_reduced(uin, cout, rho, sigma, partial, stt);
+    };
+    const bool all_blocked = m > 0 && M.P.blocked && M.A.blocked && At.blocked;
+    const int parts_op = cg_explicit ? dot_parts(L.mat) : (all_blocked ? nb_n : (m > 0 ? dot_parts(At) : dot_parts(M.P)));
+    const bool fused_pa = PA.blocked && !cg_explicit;
+    apply_op(xx, cc, nullptr, nullptr);
+    T* ub[2] = {cu, cu2}; int ui = 0;                            // ub[ui] = current direction u
+    hipLaunchKernelGGL((k_cg_init<T>), dim3(nb_n), dim3(256), 0, st, (int)n, tt, cc, cr, ub[ui], part_rr);
+    hipLaunchKernelGGL(k_cg_init_final, dim3(1), dim3(256), 0, st, nb_n, part_rr, slot[cur], eps_pcg,
+                       sizeof(T) == 8 ? 1.4901161193847656e-08 : 3.4526698300124393e-04, itr_pcg);
+    // Launch batches: the first one is the previous call's iteration count (consecutive ADMM iterations need nearly the same number); every further
+    // one is what the measured contraction says is left (res_end / res_init over the iterations run so far), at least one and never more than doubles
+    // the total.  An iteration enqueued past convergence still costs four dispatches that return at the done flag: with "last + 1, then double" a
+    // sixth of the product dispatches of BASELINE config 3 were such no-ops (profiles/r03_z_bench_c3_kernel_stats.csv).
+    HIPC(hipMemcpyAsync(state_host + 1, slot[cur], sizeof(CgState), hipMemcpyDeviceToHost, st));   // the initial residual, read at the first synchronisation
+    int launched = 0, batch = std::max(1, std::min(last_cg, 64));
+    for (;;) {
+        for (int b = 0; b < batch; ++b) {
+            ProfScope ps(prof, cat_op, 2);
+            // fold the previous iteration's ||r||^2, publish the scalars into the other slot, u = r + beta u
+            if (fused_pa) {
+                // [P; A] u with u = r + beta u_old formed while the x blocks are loaded; then A'(A u); ONE combine for c and dot(u, c)
+                CgFuse<T> fu; fu.r = cr; fu.uold = ub[ui]; fu.unew = ub[ui ^ 1]; fu.part_rr = part_rr; fu.nparts = nb_n;
+                fu.cur = slot[cur]; fu.nxt = slot[cur ^ 1]; fu.first = b == 0 ? 1 : 0;
+                // level 1: the two products of the first CG iteration of every 8th cg() call are timed by their own dispatch timestamps
+                const bool sample = prof.level == 2 || (prof.level == 1 && b == 0 && launched == 0 && prof_calls % 8 == 0);
+                { ProfLaunchScope ps2(prof, cat_pa, sample ? 1 : 3); spmv_blk(st, PA, cr, nullptr, fu); }
+                cur ^= 1; ui ^= 1;
+                const T* pp = static_cast<const T*>(PA.partial);
+                const int nb_m = (int)((m + 255) / 256);
+                hipLaunchKernelGGL((k_cg_combine_pa<T>), dim3((unsigned)(nb_n + nb_m)), dim3(256), 0, st, (int)n, (int)m, nb_n, pp, PA.nblk, (int64_t)(n + m), ub[ui],
+                                   (T)sigma, (T)rho, cc, tm, part_uc, slot[cur]);                       // cc = P u, tm = A u, partials of dot(u, c)
+                { ProfLaunchScope ps2(prof, cat_at, sample ? 1 : 3); spmv_blk(st, At, tm, slot[cur]); }
+                hipLaunchKernelGGL((k_cg_combine_update<T>), dim3(nb_n), dim3(256), 0, st, (int)n, cc, static_cast<const T*>(At.partial), At.nblk, (int64_t)n, (T)rho,
+                                   (T)sigma, ub[ui], nb_n + nb_m, part_uc, xx, cr, part_rr, slot[cur]);
+                continue;
+            } else {
+                hipLaunchKernelGGL((k_cg_next_u<T>), dim3(nb_n), dim3(256), 0, st, (int)n, nb_n, part_rr, cr, ub[ui], slot[cur], slot[cur ^ 1], b == 0 ? 1 : 0);
+                cur ^= 1;
+                apply_op(ub[ui], cc, part_uc, slot[cur]);
+            }
+            hipLaunchKernelGGL((k_cg_update_xr<T>), dim3(nb_n), dim3(256), 0, st, (int)n, parts_op, part_uc, ub[ui], cc, xx, cr, part_rr, slot[cur]);
+        }
+        hipLaunchKernelGGL(k_cg_finish, dim3(1), dim3(256), 0, st, nb_n, part_rr, slot[cur]);   // fold the last iteration of the batch
+        launched += batch;
+        HIPC(hipMemcpyAsync(state_host, slot[cur], sizeof(CgState), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+        if (state_host->done || launched >= itr_pcg) break;
+        {
+            const double r0 = std::sqrt(state_host[1].res2), r1 = std::sqrt(state_host->res2), tol = state_host->tol;
+            int left = std::max(launched, 1);                                                   // no usable rate: as many again
+            if (r1 > 0 && r0 > r1 && tol > 0 && r1 > tol) {
+                const double per_it = std::log(r0 / r1) / std::max(1, state_host->iters);       // contraction per iteration so far
+                left = (int)std::ceil(std::log(r1 / tol) / per_it);
+            }
+            batch = std::max(1, std::min(std::min(std::max(left, 2), std::max(launched, 2)), std::min(64, itr_pcg - launched)));   // (two at least: a synchronisation costs about one iteration)
+        }
+    }
+    last_cg = state_host->iters;
+    ++prof_calls;
+    cg_total += state_host->iters;
+    return state_host->iters;
+}
+
+template struct SparseMatrices<double>;
+template struct SparseMatrices<float>;
+template struct CgPlugin<double>;
+template struct CgPlugin<float>;
 
 }  // namespace qps
+
 
 #ifdef QPS_SPMV_STAMPS
 extern "C" __attribute__((visibility("default"))) int qps_debug_spmv_stamps(long long* out, int count, int filter_rows) {

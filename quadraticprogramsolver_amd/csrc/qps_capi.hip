@@ -1,6 +1,6 @@
 // qps_capi.hip -- the C ABI of include/qps.h and nothing else: the handle table, argument validation and problem import of every entry point.  The solvers live
 // behind factories: make_dense (qps_dense.hip), make_dense_batch (qps_dense_batch.hip), the shared-matrix batches (qps_shared_batch.hip), make_sparse_solver
-// (k_sparse.hip) and ProxQP (qps_proxqp.hip); the per-device resource pools are in qps_runtime.hip.
+// (qps_sparse.hip) and ProxQP, dense and sparse (qps_proxqp.hip); the per-device resource pools are in qps_runtime.hip.
 //
 // An entry point tests its arguments in a fixed order and words every refusal itself; tests/test_capi_errors_cpu.py pins status, text and order.
 // There is NO CPU fallback: without a HIP device every entry point fails with QPS_ERR_NO_DEVICE.
@@ -585,7 +585,7 @@ QPS_API int32_t qps_proxqp_create_dense(int64_t n, int64_t me, int64_t mi, const
     return create_handle(device, n, me + mi, out, [&](Handle& h) { h.proxqp = make_proxqp(device, n, me, mi, dtype, P, ldp, A, lda, b, C, ldc, d, q); });
 }
 // SparseProxQP (ProxQP.jl:71, :95-115): the CSC fields of the three SparseMatrixCSC inputs, kept sparse.  The linear system of UpdateX! is solved
-// in its KKT form by the sparse L D L' plugin (k_sparse.hip: SparseProxQpSolver): symbolic analysis once, a rho update re-factorises numerically
+// in its KKT form by the sparse L D L' plugin (qps_proxqp.hip: SparseProxQpSolver): symbolic analysis once, a rho update re-factorises numerically
 // on the frozen pattern -- the role of AlignSparsePattern / GetNzvalDiagIdxs / UpdateM! / the pattern-reusing cholesky! (:184-190, :201-206, :335-372).
 // QPS_PROXQP_SPARSE=0 densifies the inputs onto the dense solver instead (in-place dense re-factorisation, :193-199).
 QPS_API int32_t qps_proxqp_create_csc(int64_t n, int64_t me, int64_t mi, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const double* q,

@@ -232,6 +232,7 @@ struct Arena {
 // Per-device recycling of what a dense handle needs besides its data: the stream, the pinned read-back block and (for small
 // problems) the device block itself.  hipStreamCreate / hipHostMalloc / hipMalloc and their counterparts cost ~3 ms per handle --
 // five times a whole solve at the reference's test sizes, where every SolveQuadraticProgram! call builds and drops a handle.
+constexpr size_t kPinnedBytes = 512;   // the pinned read-back block of a handle
 struct HandleResources { hipStream_t st = nullptr; void* pinned = nullptr; char* block = nullptr; size_t block_bytes = 0; };
 HandleResources acquire_resources(int device, size_t block_need);      // block may come back null (caller allocates)
 void recycle_resources(int device, HandleResources r);                  // stream must be idle
@@ -262,6 +263,7 @@ struct SolverBase {
 };
 
 
+// CSC handle, CG and direct KKT plugins (qps_sparse.hip): canonical copies of the caller's CSC are made inside
 SolverBase* make_sparse_solver(int device, int64_t n, int64_t m, int dtype, const int64_t* Pcp, const int64_t* Pri,
                                const double* Pnz, const int64_t* Acp, const int64_t* Ari, const double* Anz, const double* q,
                                const double* l, const double* u, int index_base);

@@ -3,6 +3,8 @@
 #pragma once
 #include <cstdint>
 #include <memory>
+#include <stdexcept>
+#include <vector>
 
 #include "ldl_symbolic.h"
 #include "qps_internal.h"
@@ -55,6 +57,51 @@ template <typename T> struct SparseLdl {
 // Pvals / Avals: the caller's CSC value arrays (P full symmetric storage), same order as the index arrays given to ldl_analyze
 template <typename T>
 std::unique_ptr<SparseLdl<T>> make_sparse_ldl(hipStream_t st, LdlSymbolic&& sym, const double* Pvals, int64_t pnnz, const double* Avals, int64_t annz);
+
+// Canonical 0-based host CSC copies of P (n x n, full symmetric storage) and A (m x n): what the analysis of a KKT factor reads.  Kept until the factor
+// that needs them exists, then released.
+struct KktHostCsc {
+    std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz;
+    bool released() const { return Pcp.empty() || Acp.empty(); }
+    void release() {
+        for (auto* v : {&Pcp, &Pri, &Acp, &Ari}) std::vector<int64_t>().swap(*v);
+        std::vector<double>().swap(Pnz); std::vector<double>().swap(Anz);
+    }
+    // ordering + symbolic analysis of [P + sigma I, A'; A, -I / rho] and the device object on it; a pattern the level-scheduled plugin cannot hold is
+    // QPS_ERR_UNSUPPORTED with the analysis' own text
+    template <typename T> std::unique_ptr<SparseLdl<T>> make_factor(hipStream_t st, int64_t n, int64_t m, const LdlLimits& lim) const {
+        LdlSymbolic sym;
+        try { sym = ldl_analyze((int)n, (int)m, Pcp.data(), Pri.data(), Acp.data(), Ari.data(), 0, lim.max_tail, lim.min_level_width, lim.max_levels); }
+        catch (const std::runtime_error& e) { throw QpsError(QPS_ERR_UNSUPPORTED, e.what()); }
+        return make_sparse_ldl<T>(st, std::move(sym), Pnz.data(), (int64_t)Pnz.size(), Anz.data(), (int64_t)Anz.size());
+    }
+};
+
+// The direct KKT plugin of a CSC handle (LinearSystemSolvers.jl:16-107): built on first use from the canonical host copies, one numeric factor cached per (rho, sigma)
+template <typename T> struct KktPlugin {
+    hipStream_t st = nullptr; int64_t n = 0, m = 0;
+    KktHostCsc host;
+    std::unique_ptr<SparseLdl<T>> ldl; bool valid = false; double rho = 0, sigma = 0;
+    int num_factorizations = 0; bool unfit = false;   // unfit: the analysis refused this pattern once (AUTO then goes to CG without asking again)
+    KktPlugin(hipStream_t st_, int64_t n_, int64_t m_) : st(st_), n(n_), m(m_) {}
+    bool released() const { return host.released(); }   // the host copies went into the factor: a later CG request stays matrix-free (explicit_prepare)
+    // LaLdlInit / QDLdlInit / FacLdlInit (LinearSystemSolvers.jl:16-24, :47-55, :78-86): ordering + symbolic once per handle, numeric per (rho, sigma)
+    void prepare(double rho_, double sigma_, bool force) {
+        if (!ldl) {
+            if (n + m > 2000000000LL) throw QpsError(QPS_ERR_BAD_DIMENSION, "KKT matrix too large for the sparse direct plugin");
+            // read at every analysis (once per handle), not once per process: the limits are part of a handle's layout
+            ldl = host.template make_factor<T>(st, n, m, ldl_limits_from_env());
+            valid = false;
+            host.release();                                                                         // the canonical host copies have served their purpose
+        }
+        if (force || !valid || rho != rho_ || sigma != sigma_) {
+            valid = false;
+            ++num_factorizations;
+            ldl->factorize(rho_, sigma_);
+            valid = true; rho = rho_; sigma = sigma_;
+        }
+    }
+};
 
 // Dense signed Cholesky M = Lt J Lt' (J = diag(sgn), sgn = +-1 known beforehand: quasi-definite matrices) of an NP x NP row-major
 // matrix (lower), in place; dinv receives the inverses of the 64 x 64 diagonal blocks of Lt, W (NP x NP scratch) the panels Lt J.

@@ -9,7 +9,7 @@
 
 namespace qps {
 namespace {
-constexpr size_t kPinnedBytes = 512, kRecycleBlockMax = (size_t)512 << 20;   // blocks above 512 MiB go back to the driver (at most 4 x that per device stay cached, of 288 GB)
+constexpr size_t kRecycleBlockMax = (size_t)512 << 20;   // blocks above 512 MiB go back to the driver (at most 4 x that per device stay cached, of 288 GB)
 constexpr int kRecyclePerDevice = 4;
 std::mutex g_res_mu;
 std::vector<HandleResources> g_res[kMaxDevices];

@@ -2,11 +2,15 @@
 plugin calls of a dense handle.  One dump per build, each in a fresh process; `compare` then demands that every array and every qps_info field except the
 times is bitwise equal.  Not a test.
 
-    python tests/tools/gpu_refactor_dump.py dump OUT.npz [--lib PATH/libqps_hip.so]
+    python tests/tools/gpu_refactor_dump.py dump OUT.npz [--lib PATH/libqps_hip.so] [--group dense|sparse]
     python tests/tools/gpu_refactor_dump.py compare A.npz B.npz
-    python tests/tools/gpu_refactor_dump.py cycle [--lib PATH] [--cycles N]     # create + solve + destroy at 64 x 128: median microseconds per cycle
+    python tests/tools/gpu_refactor_dump.py cycle [--lib PATH] [--cycles N] [--group dense|sparse]   # create + solve + destroy at 64 x 128 (sparse: of a small
+                                                                                # CSC and a small sparse ProxQP handle): median microseconds per cycle
 
-The routes are those named in tests/loop_param_cases.py."""
+The routes are those named in tests/loop_param_cases.py.  `--group sparse` covers the CSC handle instead -- the CG plugin on every product form, the explicit
+reduced matrix, the direct KKT plugin, AUTO, polishing, the plugin calls, the five operators -- and the sparse ProxQP form.  QPS_GRAPH is read once per process: a
+dump started with QPS_GRAPH=0 runs the direct plugin's routes alone, eagerly, under their own tags."""
+import contextlib
 import os
 import sys
 import time
@@ -111,6 +115,134 @@ def dump(q, path):
     print("wrote", path, len(out), "arrays")
 
 
+@contextlib.contextmanager
+def environment(**kw):
+    """The QPS_* variables a handle reads at creation (or a request when it is served), set for the duration of one route."""
+    old = {k: os.environ.get(k) for k in kw}
+    os.environ.update(kw)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+
+
+def sparse_qp(n, m, seed, per_row=8.0):
+    """P = M'M + I (M with 3 entries per column), A with `per_row` entries per row, bounds of width <= 2 around A x0."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    M = sp.random(n, n, density=3.0 / n, random_state=rng, data_rvs=rng.standard_normal, format="csc")
+    P = (M.T @ M + sp.identity(n)).tocsc()
+    A = sp.random(m, n, density=min(1.0, per_row / n), random_state=rng, data_rvs=rng.standard_normal, format="csc") if m else sp.csc_matrix((0, n))
+    Ax = A @ rng.standard_normal(n)
+    return P, rng.standard_normal(n), A, Ax - rng.random(m), Ax + rng.random(m)
+
+
+FORMS = {"stream": dict(QPS_SPMV_BLOCKED="0"), "task": dict(QPS_SPMV_BLOCKED="1", QPS_SPMV_SELL="0"), "sell": dict(QPS_SPMV_BLOCKED="1", QPS_SPMV_SELL="1")}
+
+
+def dump_sparse(q, path):
+    from quadraticprogramsolver_amd import _lib
+    from quadraticprogramsolver_amd.proxqp import ProxQP, SolveQuadraticProgramProxQP
+    import scipy.sparse as sp
+    out = {}
+    eager = os.environ.get("QPS_GRAPH") == "0"
+    small, mid = sparse_qp(600, 400, 1), sparse_qp(16000, 9000, 2)       # mid: three column blocks in fp64, two in fp32
+
+    def solve(tag, prob, linsys, dtype, reps=1, env=None, kinds=None, **kw):
+        """One handle, `reps` solves (reuseFactor from the second on; kinds: the linsys constant of each solve when it changes on the handle)."""
+        P, qq, A, l, u = prob
+        base = dict(numIterations=40, numItrConv=10, ϵAbs=1e-6, ϵRel=1e-6, ρ=RHO)
+        base.update(kw)
+        with environment(**(env or {})), q.QuadraticProgram(P, qq, A, l, u, linsys=linsys, dtype=dtype) as h:
+            for r in range(reps):
+                if kinds:
+                    h.linsys = kinds[r]
+                x = np.zeros(P.shape[0]); info = {}
+                t = f"{tag}.{dtype}" + (f".solve{r}" if reps > 1 else "")
+                try:
+                    h.solve(x, info=info, **dict(base, reuseFactor=(r > 0 and not kinds)))
+                except q.QpsError as e:                                          # a refusal is part of the record: its text must not move
+                    out[t + "/refused"] = np.frombuffer(str(e).encode(), dtype=np.uint8)
+                    print(f"{t:44s} refused: {e}", flush=True)
+                    continue
+                keys, vals = info_array(info)
+                z, y = h.dual()
+                out[t + "/X"], out[t + "/Z"], out[t + "/Y"], out[t + "/info"] = x, np.array(z), np.array(y), vals
+                print(f"{t:44s} " + " ".join(f"{k}={info[k]:g}" for k in ("convFlag", "iterations", "numRefactor", "cgIterations", "cgExplicit", "polishFlag")), flush=True)
+
+    for dtype in ("f64", "f32"):
+        ldl = dict(numIterations=100, numItrConv=25)
+        sfx = ".eager" if eager else ""
+        solve("ldl" + sfx, small, "ldl", dtype, **ldl)
+        solve("ldl_every_iteration_checked" + sfx, small, "ldl", dtype, numIterations=30, numItrConv=1, ϵAbs=0.0, ϵRel=0.0)
+        solve("ldl_adaptive" + sfx, small, "ldl", dtype, adptΡ=True, fctrΡ=1.0, numItrConv=5, numIterations=60, ϵAbs=0.0, ϵRel=0.0)
+        solve("ldl_reuse_factor" + sfx, small, "ldl", dtype, reps=2, **ldl)
+        if eager:
+            continue
+        nocg = dict(QPS_CG_EXPLICIT="0")
+        for form, env in FORMS.items():
+            solve("cg_matfree_" + form, mid, "cg", dtype, env=dict(env, **nocg))
+            solve("cg_matfree_m0_" + form, sparse_qp(6000, 0, 3), "cg", dtype, env=dict(env, **nocg))
+            solve("cg_explicit_adaptive_" + form, small, "cg_explicit", dtype, env=env, adptΡ=True, fctrΡ=1.0, numItrConv=5, numIterations=30, ϵAbs=0.0, ϵRel=0.0)
+        for fuse in "01":
+            solve("cg_matfree_sell_fusepa" + fuse, mid, "cg", dtype, env=dict(FORMS["sell"], QPS_SPMV_FUSEPA=fuse, **nocg))
+        solve("auto_small", small, "cg", dtype, kinds=[_lib.QPS_LINSYS_AUTO])
+        solve("auto_mid", mid, "cg", dtype, kinds=[_lib.QPS_LINSYS_AUTO])
+        solve("ldl_then_cg_explicit", small, "ldl", dtype, reps=2, kinds=[_lib.QPS_LINSYS_KKT_LDL, _lib.QPS_LINSYS_CG_EXPLICIT])
+        solve("polish_cg", small, "cg", dtype, polish=True, numIterations=400, env=nocg)
+        solve("polish_ldl", small, "ldl", dtype, polish=True, numIterations=400)
+
+        # the plugin calls and the five operators
+        rng = np.random.default_rng(5)
+        for linsys, form in (("cg", "stream"), ("cg", "sell"), ("cg_explicit", "stream"), ("cg_explicit", "task"), ("ldl", "stream")):
+            P, qq, A, l, u = mid if linsys == "cg" else small
+            n, m = P.shape[0], A.shape[0]
+            x, z, y = rng.standard_normal(n), rng.standard_normal(m), rng.standard_normal(m)
+            with environment(**dict(FORMS[form], **(nocg if linsys == "cg" else {}))), q.QuadraticProgram(P, qq, A, l, u, linsys=linsys, dtype=dtype) as h:
+                h.linsys_init(RHO, 1e-6)
+                for t, rho, changed in (("changed0", RHO, False), ("changed1", 0.3, True)):
+                    xx, zz = np.zeros(n), np.zeros(m)
+                    h.linsys_solve(x, z, y, rho, 1e-6, changed, xx, zz)
+                    out[f"linsys_solve.{linsys}.{form}.{t}.{dtype}/xx"], out[f"linsys_solve.{linsys}.{form}.{t}.{dtype}/zz"] = xx, zz
+                if linsys == "cg":
+                    for op in ("P", "A", "At", "PA", "reduced"):
+                        out[f"operator_apply.{form}.{op}.{dtype}"] = np.array(h.apply(op, z if op == "At" else x, ρ=0.7, σ=0.01))
+        print(f"plugin calls {dtype}: linsys_init, linsys_solve x 2 on five handles; operator_apply x 5 stream and sliced (stacked [P; A])", flush=True)
+
+        # the sliced form staged and lane by lane: a workgroup's share of the rows reaches 1024 only at n = 50 000, m = 100 000 (tests/test_gpu_spmv_operator.py)
+        big = sparse_qp(50000, 100000, 4)
+        for staged in "10":
+            solve("cg_matfree_sell_staged" + staged, big, "cg", dtype, env=dict(FORMS["sell"], QPS_SPMV_STAGED=staged, **nocg), numIterations=4, numItrConv=2)
+
+        # sparse ProxQP
+        def proxqp(tag, n, me, mi, explicit_state=False, env=None, **kw):
+            r = np.random.default_rng(11)
+            P = small[0] if n == 600 else sparse_qp(n, 0, 6)[0]
+            A = sp.random(me, n, density=8.0 / n, random_state=r, data_rvs=r.standard_normal, format="csc") if me else sp.csc_matrix((0, n))
+            Cm = sp.random(mi, n, density=8.0 / n, random_state=r, data_rvs=r.standard_normal, format="csc") if mi else sp.csc_matrix((0, n))
+            x0 = r.standard_normal(n)
+            args = (P, r.standard_normal(n), A, A @ x0, Cm, Cm @ x0 + r.random(mi))
+            if explicit_state:
+                args += (0.1 * r.standard_normal(n), np.zeros(me), np.zeros(mi), np.ones(mi))
+            with environment(**(env or {})), ProxQP(*args, dtype=dtype) as pq:
+                rep = SolveQuadraticProgramProxQP(pq, **dict(dict(numIterations=60, numItrConv=10), **kw))
+                t = f"proxqp_{tag}.{dtype}"
+                out[t + "/X"], out[t + "/Y"], out[t + "/Z"], out[t + "/S"] = pq.vX.copy(), pq.vY.copy(), pq.vZ.copy(), pq.vS.copy()
+                out[t + "/report"] = np.array([float(rep[k]) for k in sorted(rep)])
+                print(f"{t:44s} " + " ".join(f"{k}={rep[k]:g}" for k in sorted(rep)), flush=True)
+
+        proxqp("init_kkt", 600, 100, 300)
+        proxqp("set_state", 600, 100, 300, explicit_state=True)
+        proxqp("no_equalities", 600, 0, 300)
+        proxqp("no_inequalities", 600, 100, 0)
+        proxqp("rho_update", 600, 100, 300, ρ=1e-2, numIterations=100)
+        proxqp("fixed_rho", 600, 100, 300, adptΡ=False)
+        proxqp("gx_from_solve", 600, 100, 300, env=dict(QPS_PROXQP_GX_SOLVE="1"))
+    np.savez(path, **out)
+    print("wrote", path, len(out), "arrays")
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = sorted(set(A.files) ^ set(B.files))
@@ -137,13 +269,61 @@ def cycle(q, cycles):
     print(f"create+solve+destroy 64x128: median_us={np.median(ts):.1f} min_us={ts.min():.1f} p90_us={np.percentile(ts, 90):.1f} cycles={cycles}")
 
 
+def cycle_sparse(q, cycles):
+    """create + solve + destroy of a small CSC handle on the CG and on the direct plugin and of a small sparse ProxQP handle (create + init_kkt + solve + destroy);
+    then the device bytes one sparse ProxQP handle holds (free memory before and after its creation, pools warm), small and with the column-blocked copies forced."""
+    import ctypes
+    import scipy.sparse as sp
+    from quadraticprogramsolver_amd.proxqp import ProxQP, SolveQuadraticProgramProxQP
+    P, qq, A, l, u = sparse_qp(600, 400, 1)
+    r = np.random.default_rng(11)
+
+    def proxqp_args(n, me, mi):
+        Pn = P if n == 600 else sparse_qp(n, 0, 6)[0]
+        Ae = sp.random(me, n, density=8.0 / n, random_state=r, data_rvs=r.standard_normal, format="csc")
+        Cm = sp.random(mi, n, density=8.0 / n, random_state=r, data_rvs=r.standard_normal, format="csc")
+        x0 = r.standard_normal(n)
+        return (Pn, r.standard_normal(n), Ae, Ae @ x0, Cm, Cm @ x0 + r.random(mi))
+
+    pq_args = proxqp_args(600, 100, 300)
+
+    def csc(linsys):
+        x = np.zeros(600)
+        with q.QuadraticProgram(P, qq, A, l, u, linsys=linsys) as h:
+            h.solve(x, numIterations=50, ρ=RHO)
+
+    def proxqp():
+        with ProxQP(*pq_args) as pq:
+            SolveQuadraticProgramProxQP(pq, numIterations=20, numItrConv=10)
+
+    for name, f in (("csc cg 600x400", lambda: csc("cg")), ("csc ldl 600x400", lambda: csc("ldl")), ("sparse proxqp 600, 100 + 300", proxqp)):
+        ts = []
+        for k in range(cycles + 20):
+            t0 = time.perf_counter(); f(); ts.append(time.perf_counter() - t0)
+        ts = np.array(ts[20:]) * 1e6
+        print(f"create+solve+destroy {name}: median_us={np.median(ts):.1f} min_us={ts.min():.1f} p90_us={np.percentile(ts, 90):.1f} cycles={cycles}", flush=True)
+    hip = ctypes.CDLL("libamdhip64.so")
+
+    def free_bytes():
+        a, b = ctypes.c_size_t(), ctypes.c_size_t()
+        assert hip.hipMemGetInfo(ctypes.byref(a), ctypes.byref(b)) == 0
+        return a.value
+
+    for name, args, env in (("600, 100 + 300", pq_args, {}), ("20000, 2000 + 30000, blocked copies forced", proxqp_args(20000, 2000, 30000), dict(QPS_SPMV_BLOCKED="1"))):
+        with environment(**env):
+            before = free_bytes()
+            with ProxQP(*args, *(np.zeros(args[0].shape[0]), np.zeros(args[2].shape[0]), np.zeros(args[4].shape[0]), np.ones(args[4].shape[0]))):
+                held = before - free_bytes()
+        print(f"device bytes held by one sparse proxqp handle ({name}): {held}", flush=True)
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     if argv and argv[0] == "dump":
-        dump(library(argv), argv[1])
+        (dump_sparse if "sparse" in argv[2:] else dump)(library(argv), argv[1])
     elif argv and argv[0] == "compare":
         sys.exit(compare(argv[1], argv[2]))
     elif argv and argv[0] == "cycle":
-        cycle(library(argv), int(argv[argv.index("--cycles") + 1]) if "--cycles" in argv else 300)
+        (cycle_sparse if "sparse" in argv[1:] else cycle)(library(argv), int(argv[argv.index("--cycles") + 1]) if "--cycles" in argv else 300)
     else:
         raise SystemExit(__doc__)
