@@ -394,6 +394,27 @@ int32_t qps_create_csc_shared_batch(int64_t count, int64_t n, int64_t m, const i
                                     const int64_t *A_colptr, const int64_t *A_rowval, const double *A_nzval, const double *q, const double *l,
                                     const double *u, int32_t index_base, int32_t dtype, int32_t device, qps_handle *out);
 
+/* Matrix-free CG shared-matrix batch: the same family on ONE sparse P and ONE sparse A (CSC as above) with the matrix-free CG plugin (QPS_LINSYS_CG,
+ * LinearSystemSolvers.jl:145-186) as its linear system -- for patterns that fill in under any ordering, which the L D L' handle refuses or cannot afford.
+ * Nothing is analysed or factorised: every ADMM iteration runs one cg! per column, all columns in lockstep on 16-column panels, so the indices and values of
+ * P, A and A' are read once per CG iteration for 16 columns and the four launches of a CG iteration are paid once per batch.  Every column has its own CG scalars
+ * (tolerance max(sqrt(eps) ||r0||, epsPcg), at most numItrPcg iterations, x~ warm-started from the previous ADMM iteration and zero at the start of a solve) and
+ * is a no-op from its last CG iteration on.
+ * Arguments are validated as by qps_create_csc_shared_batch, in the same order, before a device is needed; instead of the n + m limit of the KKT matrix:
+ * QPS_ERR_BAD_DIMENSION for n or m above 2^31 - 64.  QPS_ERR_UNSUPPORTED from the create call: m = 0.
+ * The handle is a shared-matrix batch handle: qps_solve_batch, qps_get_dual, qps_update_shared_vectors, every qps_set_shared_* option but the equilibration,
+ * qps_polish_shared, qps_set_profiling, qps_kernel_times, qps_last_error and qps_destroy work on it, and column b behaves as a stand-alone qps_solve on a CSC
+ * handle with QPS_LINSYS_CG, matrix-free, at a fixed rho, with epsPcg and numItrPcg of qps_params: its own check, flag, iteration count and residuals.  Inner
+ * products are added in an order that depends on n and the matrices only: a column of a batch equals the same data in a batch of one bit for bit.
+ * A family-wide rho switch (qps_set_shared_adaptive_rho) and a per-row rho scale cost no factorisation here; numRefactor, rhoFinal and rhoProposed report the
+ * switches as on the other handles.  qps_info.cgIterations of column b: the CG iterations of that column summed over the ADMM iterations of the solve.
+ * qps_solve_batch refuses with QPS_ERR_UNSUPPORTED (the handle stays usable): adptRho != 0, polish != 0, a linsys other than QPS_LINSYS_AUTO or QPS_LINSYS_CG;
+ * with QPS_ERR_BAD_ARGUMENT: an epsPcg that is negative or not finite, numItrPcg < 1.  reuseFactor, trsvBlock and loopVariant are accepted and without effect.
+ * qps_set_shared_equilibration with passes > 0: QPS_ERR_UNSUPPORTED (passes = 0 is a no-op; qps_get_shared_equilibration returns ones). */
+int32_t qps_create_csc_shared_batch_cg(int64_t count, int64_t n, int64_t m, const int64_t *P_colptr, const int64_t *P_rowval, const double *P_nzval,
+                                       const int64_t *A_colptr, const int64_t *A_rowval, const double *A_nzval, const double *q, const double *l,
+                                       const double *u, int32_t index_base, int32_t dtype, int32_t device, qps_handle *out);
+
 /* The per-problem loop of RunBenchmarks.jl:88-104 sharded over the devices of ONE process ("one host thread + one stream per device", "work-stealing at
  * chunk boundaries").  `count` independent dense QPs of one shape, arrays stacked as for qps_create_dense_batch; `devices[num_workers]` lists the device of every worker
  * -- one host thread each; a device may be listed more than once (two workers sharing a card).  Every worker repeatedly takes the next range of QPs from a shared

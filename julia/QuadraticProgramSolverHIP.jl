@@ -384,6 +384,24 @@ function SharedBatchCreate(mP::SparseMatrixCSC{Float64, Int64}, mQ::Matrix{Float
     return SharedBatchHip(h[], n, m, count)
 end
 
+# The same family with the matrix-free CG plugin as its linear system (qps_create_csc_shared_batch_cg): for patterns that fill in under any ordering.  Nothing is
+# analysed or factorised; every iteration runs one cg! per column (LinOpCg!, LinearSystemSolvers.jl:164-186), all columns in lockstep on 16-column panels, with
+# ϵPcg / numItrPcg of SharedBatchSolve!.  The handle is a SharedBatchHip; SharedBatchSetEquilibration! with a positive pass count is refused by the library.
+function SharedBatchCreateCg(mP::SparseMatrixCSC{Float64, Int64}, mQ::Matrix{Float64}, mA::SparseMatrixCSC{Float64, Int64}, mL::Matrix{Float64}, mU::Matrix{Float64};
+    device = 0, dtype::Type = Float64)
+    n = size(mP, 1); m = size(mA, 1); count = size(mQ, 2)
+    size(mP, 2) == n || throw(DimensionMismatch("The matrix mP must be square"))
+    size(mA, 2) == n || throw(DimensionMismatch("The number of columns of mA must match mP"))
+    size(mQ, 1) == n || throw(DimensionMismatch("mQ must be n x count"))
+    (size(mL) == (m, count) && size(mU) == (m, count)) || throw(DimensionMismatch("mL and mU must be m x count"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mP mA mQ mL mU _check(ccall((:qps_create_csc_shared_batch_cg, LIBQPS), Int32,
+        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+        count, n, m, mP.colptr, mP.rowval, mP.nzval, mA.colptr, mA.rowval, mA.nzval, mQ, mL, mU, Int32(1), _dtype(dtype), Int32(device), h))   # index_base = 1
+    return SharedBatchHip(h[], n, m, count)
+end
+
 function SharedBatchUpdate!(sb::SharedBatchHip; mQ::Union{Nothing, Matrix{Float64}} = nothing, mL::Union{Nothing, Matrix{Float64}} = nothing,
     mU::Union{Nothing, Matrix{Float64}} = nothing)
     h = sb.h
@@ -456,10 +474,11 @@ end
 EqualityRhoScale(mL::Matrix{Float64}, mU::Matrix{Float64}; factor = 1e3) = [all(mL[i, :] .== mU[i, :]) ? Float64(factor) : 1.0 for i in 1:size(mL, 1)]
 
 function SharedBatchSolve!(sb::SharedBatchHip, mX::Matrix{Float64}; numIterations = 5000, ϵAbs = 1e-6, ϵRel = 1e-6, ρ = 1, σ = 1e-6, α = 1.6,
-    fctrΡ = 5, numItrConv = 25, reuseFactor::Bool = false, numItrPolish = 10, δ = 1e-6, ϵMinres = 1e-6, numItrMinres = 500)
+    fctrΡ = 5, numItrConv = 25, reuseFactor::Bool = false, numItrPolish = 10, δ = 1e-6, ϵMinres = 1e-6, numItrMinres = 500,
+    ϵPcg = 1e-6, numItrPcg = 1000)             # abstol and maxiter of every column's cg! on a SharedBatchCreateCg handle; the other handles do not read them
     h = sb.h; count = sb.count
     size(mX) == (sb.n, count) || throw(DimensionMismatch("mX must be n x count: the library reads and writes count columns of length n"))
-    prm = QpsParams(numIterations, 0, numItrConv, numItrPolish, numItrMinres, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, δ, fctrΡ, ϵMinres, 1e-6, 1000, 0, 0, 0)   # the polishing kwargs act under SharedBatchSetPolish!
+    prm = QpsParams(numIterations, 0, numItrConv, numItrPolish, numItrMinres, 0, 0, reuseFactor, ϵAbs, ϵRel, ρ, σ, α, δ, fctrΡ, ϵMinres, ϵPcg, numItrPcg, 0, 0, 0)   # the polishing kwargs act under SharedBatchSetPolish!
     buf = Vector{UInt8}(undef, count * sizeof(QpsInfo))
     GC.@preserve mX buf _check(ccall((:qps_solve_batch, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{QpsParams}, Ptr{UInt8}),
                                      h, mX, Ref(prm), buf), h)

@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "qps_create_dense_shared_batch", "qps_update_shared_vectors", "qps_create_csc_shared_batch", "qps_set_shared_rho_scale",
     "qps_set_shared_adaptive_rho", "qps_set_shared_equilibration", "qps_get_shared_equilibration", "qps_set_shared_warm_start", "qps_set_shared_dual",
     "qps_set_shared_infeasibility", "qps_get_shared_certificate", "qps_polish_shared", "qps_set_shared_polish",
+    "qps_create_csc_shared_batch_cg",
 ]
 
 QPS_OK = 0
@@ -154,6 +155,7 @@ def lib() -> C.CDLL:
     L.qps_polish_shared.argtypes = [hp, dp, dp, C.POINTER(QpsParams), C.POINTER(QpsPolishReport)]
     L.qps_set_shared_polish.argtypes = [hp, C.c_int32]
     L.qps_create_csc_shared_batch.argtypes = [i64, i64, i64, ip, ip, dp, ip, ip, dp, dp, dp, dp, i32, i32, i32, C.POINTER(hp)]
+    L.qps_create_csc_shared_batch_cg.argtypes = [i64, i64, i64, ip, ip, dp, ip, ip, dp, dp, dp, dp, i32, i32, i32, C.POINTER(hp)]
     L.qps_solve_batch_multi.argtypes = [i64, i64, i64, dp, dp, dp, dp, dp, i32, C.POINTER(i32), i32, i32, dp, C.POINTER(QpsParams), C.POINTER(QpsInfo), C.POINTER(i32), dp]
     L.qps_kernel_times.argtypes = [hp, C.POINTER(QpsKernelTime), i32, C.POINTER(i32)]
     L.qps_set_profiling.argtypes = [hp, i32]

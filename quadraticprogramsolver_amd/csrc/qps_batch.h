@@ -41,11 +41,15 @@ BatchSolverBase* make_dense_batch(int device, int dtype, int count, int64_t n, i
 struct SparseSharedInput {   // what qps_create_csc_shared_batch prepares on the host before a device is needed
     LdlSymbolic sym; std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz; int spr = 0;
 };
+struct CgSharedInput {       // what qps_create_csc_shared_batch_cg prepares on the host: the canonical CSC arrays (0-based, rows sorted, duplicates summed)
+    std::vector<int64_t> Pcp, Pri, Acp, Ari; std::vector<double> Pnz, Anz;
+};
 int shared_batch_max_np(int dtype);   // the largest padded n of a dense shared-matrix batch
 BatchSolverBase* make_dense_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda,
                                          const double* q, const double* l, const double* u);
 BatchSolverBase* make_sparse_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, SparseSharedInput&& in, const double* q, const double* l,
                                           const double* u);
+BatchSolverBase* make_cg_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, CgSharedInput&& in, const double* q, const double* l, const double* u);
 
 // column-major host matrix (rows x cols, ld ldh) -> row-major device T (ld ldd), streamed through a bounded device staging buffer in column panels
 template <typename T>

@@ -378,6 +378,26 @@ QPS_API int32_t qps_create_csc_shared_batch(int64_t count, int64_t n, int64_t m,
     return create_handle(device, n, m, out, [&](Handle& h) { h.fused_batch = make_sparse_shared_batch(device, dtype, (int)count, n, m, std::move(in), q, l, u); });
 }
 
+QPS_API int32_t qps_create_csc_shared_batch_cg(int64_t count, int64_t n, int64_t m, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const int64_t* Acp,
+                                               const int64_t* Ari, const double* Anz, const double* q, const double* l, const double* u, int32_t index_base,
+                                               int32_t dtype, int32_t device, qps_handle* out) {
+    if (const int rc = check_out(out)) return rc;
+    if (const int rc = check_count(count)) return rc;
+    if (const int rc = check_dims(n, m)) return rc;                                    // (ahead of the panel limit; check_csc_shape asks again)
+    if (n > ((int64_t)1 << 31) - 64 || m > ((int64_t)1 << 31) - 64)
+        return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "problem too large for the panel form of the matrix-free CG plugin (n, m <= 2^31 - 64)");
+    if (const int rc = check_csc_shape(n, m, Pcp, Pri, Pnz, Acp, Ari, Anz, q, l, u, index_base, dtype, count)) return rc;
+    if (m == 0) return fail_with(nullptr, QPS_ERR_UNSUPPORTED, "shared-matrix batch needs m >= 1 (without constraints the columns are independent linear solves)");
+    if (Pcp[n] - index_base > 2000000000LL || Acp[n] - index_base > 2000000000LL) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "more than 2^31 non-zeros");
+    CgSharedInput in;                                                                  // no analysis: the canonical arrays are all the host prepares
+    const int rc = guarded(nullptr, [&] {
+        layout::canonical_csc(n, Pcp, Pri, Pnz, index_base, in.Pcp, in.Pri, in.Pnz);
+        layout::canonical_csc(n, Acp, Ari, Anz, index_base, in.Acp, in.Ari, in.Anz);
+    });
+    if (rc != QPS_OK) return rc;
+    return create_handle(device, n, m, out, [&](Handle& h) { h.fused_batch = make_cg_shared_batch(device, dtype, (int)count, n, m, std::move(in), q, l, u); });
+}
+
 QPS_API int32_t qps_update_shared_vectors(qps_handle hh, const double* q, const double* l, const double* u) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     const char* other = "not a shared-matrix batch handle";   // BAD_ARGUMENT here, not the gate's UNSUPPORTED; a fused batch of another kind has its arrays tested first

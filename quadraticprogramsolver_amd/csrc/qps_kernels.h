@@ -219,6 +219,34 @@ void shared_polish_step(hipStream_t st, const SharedPolishGeom& g, SharedPolishS
 template <typename T> void shared_polish_add(hipStream_t st, const SharedPolishGeom& g, const int* live, const SharedPolishState* state, T* t, T* tt);   // t += tt (:319)
 template <typename T> void shared_polish_select(hipStream_t st, const SharedPolishGeom& g, const int* take, const T* t, T* x);   // x = t_x where take (:322-325)
 
+// ---- matrix-free CG of the shared-matrix batches (k_cg_panel.hip): LinOpCg! per column, all columns in lockstep on panels [npanel][n or m][16] ----------------
+// State: [2][16 npanel], ping-ponged by cg_panel_iteration (cur -> cur ^ 1); res2 / prev2 are the squared residual norms of cg!.  part_uc holds
+// 16 npanel * cg_panel_op_blocks(n, spr_op) doubles, part_rr 16 npanel * cg_panel_vec_blocks(n): one partial per (workgroup, column), added in workgroup order.
+struct CgPanelState { double res2, prev2, tol; int itn, done; };
+template <typename T> struct CgPanelArgs {
+    int n = 0, m = 0, npanel = 0;
+    CsrPanelMatrix<T> P, A, At;                  // A.spr: v = rho_i (A u) and the post step; At.spr: the right-hand side
+    int spr_op = 1;                              // the strips of "row r of P, then row r of A'": cg_panel_op_spr
+    const T *q = nullptr, *lo = nullptr, *hi = nullptr; T *x = nullptr, *xp = nullptr, *z = nullptr, *zp = nullptr, *y = nullptr;   // the ADMM state
+    T *xx = nullptr, *r = nullptr, *u = nullptr, *c = nullptr, *v = nullptr, *t = nullptr; const T* w = nullptr;                  // x~, cg!'s vectors, rho_i z - y
+    double *part_uc = nullptr, *part_rr = nullptr; CgPanelState* state = nullptr;
+    const int* active = nullptr;                 // one word per column
+    const T *rho_row = nullptr, *rho1_row = nullptr;   // rho_i and 1 / rho_i per row of A while a scale is set (m long)
+    T rho = T(1), sigma = T(0), alpha = T(0);
+    double eps_pcg = 0; int max_it = 0;          // abstol and maxiter of cg!
+};
+int cg_panel_op_spr(int64_t nnzP, int64_t nnzA, int n);   // from the mean of nnz(row of P) + nnz(row of A'): what one row group of the operator's second launch walks
+int cg_panel_op_blocks(int rows, int spr);                // workgroups per panel of the operator's second launch: 16 / spr rows per group, at most 2048 workgroups
+int cg_panel_vec_blocks(int rows);                        // workgroups per panel of the vector kernels: 16 rows per group, at most 256 workgroups
+// t = sigma x - q + A'w, r = t - Op(x~), u = 0, state[0 .. 16 npanel) with tol = max(sqrt(eps(T)) ||r||, eps_pcg); a column is born done when it is inactive or within tol
+template <typename T> void cg_panel_begin(hipStream_t st, const CgPanelArgs<T>& a);
+// one iteration of every column that is not done, four launches: fold + u = r + beta u (first: the scalars of `cur` are current), v = rho_i (A u),
+// c = P u + sigma u + A'v with the partials of u'c, x~ += alpha u and r -= alpha c with the partials of ||r||^2
+template <typename T> void cg_panel_iteration(hipStream_t st, const CgPanelArgs<T>& a, int cur, bool first);
+template <typename T> void cg_panel_finish(hipStream_t st, const CgPanelArgs<T>& a, int cur);   // the last ||r||^2 folded into state[cur] in place, before the host reads it
+// z~ = A x~ with SolveQuadraticProgram.jl:59-61 as its epilogue, then xp = x, x = alpha x~ + (1 - alpha) x; active columns only
+template <typename T> void cg_panel_post(hipStream_t st, const CgPanelArgs<T>& a);
+
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);
 template <typename T> void transpose_small(hipStream_t st, const T* A, int NP, int MP, T* At);

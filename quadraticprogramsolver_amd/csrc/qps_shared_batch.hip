@@ -1,7 +1,8 @@
 // qps_shared_batch.hip -- the shared-matrix batches: `count` QPs on ONE P and ONE A that differ in q, l, u only.  One host driver of the ADMM loop
-// (SharedFamilySolver: SolveQuadraticProgram.jl:36-73 for every column at once, every option of qps_set_shared_*), two linear-system paths under it: the dense
-// Cholesky on MFMA panels (SharedBatchSolver, k_shared.hip) and the sparse KKT L D L' with panel sweeps (SparseSharedBatchSolver, k_ldl.hip, k_csr_panel.hip).
-// qps_capi.hip validates the caller's arrays and builds the handles through the two factories at the end of this file.
+// (SharedFamilySolver: SolveQuadraticProgram.jl:36-73 for every column at once, every option of qps_set_shared_*), three linear-system paths under it: the dense
+// Cholesky on MFMA panels (SharedBatchSolver, k_shared.hip), the sparse KKT L D L' with panel sweeps (SparseSharedBatchSolver, k_ldl.hip, k_csr_panel.hip) and
+// the matrix-free CG on panels (CgSharedBatchSolver, k_cg_panel.hip).
+// qps_capi.hip validates the caller's arrays and builds the handles through the three factories at the end of this file.
 #include <limits>
 #include <memory>
 
@@ -73,6 +74,17 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         d_active = mem.dalloc<int>(CP, st); h_int = mem.pinned<int>(CP + 4);
         slots = mem.dalloc<unsigned long long>(16 * (int64_t)CP, st); res_dev = mem.dalloc<double>(8 * (int64_t)CP, st); res_host = mem.pinned<double>(8 * (size_t)CP);
         stage = mem.dalloc<double>((int64_t)count * std::max(n, m) + 64, st);
+    }
+    // a host CSR matrix on the device as the CSR x panel products read it (the sparse paths: the check's P, A, A'; the CG path's operator)
+    CsrPanelMatrix<T> upload_csr(const layout::CsrHost& h) {
+        CsrPanelMatrix<T> M; M.rows = h.nrows;
+        int* rp = mem.dalloc<int>((int64_t)h.rp.size(), st); int* ci = mem.dalloc<int>((int64_t)h.ci.size(), st);
+        T* va = mem.dalloc<T>((int64_t)h.va.size(), st);
+        std::vector<T> v(h.va.begin(), h.va.end());
+        up->copy(rp, h.rp.data(), sizeof(int) * h.rp.size());
+        if (!h.ci.empty()) { up->copy(ci, h.ci.data(), sizeof(int) * h.ci.size()); up->copy(va, v.data(), sizeof(T) * v.size()); }
+        M.rp = rp; M.ci = ci; M.va = va; M.spr = csr_panel_spr((int64_t)h.ci.size(), h.nrows);
+        return M;
     }
     // host [count][len] doubles -> panels (padding rows and columns zero); ordered on the stream, the host array is free when this returns
     void put_panels(const double* h, T* d, int64_t len, int rowsP) {
@@ -244,7 +256,7 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         last_conv = conv;
         for (int b = 0; b < count && infos; ++b) {
             qps_info& in = infos[b];
-            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = 0;
+            in.convFlag = conv[b]; in.iterations = iters[b]; in.numRefactor = nref[b]; in.cgIterations = (int)column_cg_iterations(b);
             in.rhoFinal = rho_col[b]; in.rhoProposed = prop_col[b]; in.resPrim = resP[b]; in.resDual = resD[b];
             in.tSetup = t1 - t0; in.tLoop = t2 - t1; in.tRefactor = tref;   // wall time of the whole batch
             in.polishFlag = -1; in.polishIterations = 0; in.tPolish = tpol;
@@ -358,6 +370,7 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     virtual void iterate(int lvl, double rho, double sigma, double alpha) = 0;        // one ADMM iteration of every active column, profiled at level `lvl`
     // Ax = A xv, Px = P xv, Aty = A'yv for arbitrary panels (the check's x, y; the certificates' dx, dyh; the polishing step's v_x, mask v_lambda); usable outside a solve
     virtual void check_products(const T* xv, const T* yv) = 0;
+    virtual int64_t column_cg_iterations(int) { return 0; }                           // qps_info.cgIterations of column b of the running solve (a path without CG: 0)
 };
 
 // =================================================================================================================
@@ -571,7 +584,7 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
     using B::q; using B::l; using B::u; using B::x; using B::xp; using B::z; using B::zp; using B::y; using B::Ax; using B::Px; using B::Aty;
     using B::d_active; using B::factor_valid; using B::fac_rho; using B::fac_sigma; using B::num_factorizations;
     using B::cat_chk; using B::cat_fac; using B::cat_switch; using B::cat_start; using B::rho_scale; using B::rs_rho; using B::rs_rho1; using B::rs_base;
-    using B::kd; using B::ke; using B::eq_kd; using B::eq_ke;
+    using B::kd; using B::ke; using B::eq_kd; using B::eq_ke; using B::upload_csr;
     std::unique_ptr<SparseLdl<T>> ldl;   // reads rs_rho / rs_rho1 in its numeric factorisation and panel kernels while a scale is set
     CsrPanelMatrix<T> P, A, At;
     LdlPanelProf pf;
@@ -618,16 +631,6 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         this->update_vectors(qh, lh, uh);
     }
     ~SparseSharedBatchSolver() override { this->drain(); }   // before ldl and its device buffers go
-    CsrPanelMatrix<T> upload_csr(const layout::CsrHost& h) {
-        CsrPanelMatrix<T> M; M.rows = h.nrows;
-        int* rp = mem.template dalloc<int>((int64_t)h.rp.size(), st); int* ci = mem.template dalloc<int>((int64_t)h.ci.size(), st);
-        T* va = mem.template dalloc<T>((int64_t)h.va.size(), st);
-        std::vector<T> v(h.va.begin(), h.va.end());
-        up->copy(rp, h.rp.data(), sizeof(int) * h.rp.size());
-        if (!h.ci.empty()) { up->copy(ci, h.ci.data(), sizeof(int) * h.ci.size()); up->copy(va, v.data(), sizeof(T) * v.size()); }
-        M.rp = rp; M.ci = ci; M.va = va; M.spr = csr_panel_spr((int64_t)h.ci.size(), h.nrows);
-        return M;
-    }
     // every value array and every vector the handle keeps between calls, in place: *= 2^(+-k) by the host exponents hd / he (device copies in kd / ke)
     void apply_equilibration(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
         const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
@@ -753,6 +756,154 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
     }
 };
 
+// =================================================================================================================
+// Matrix-free CG path (a scenario sweep on a model whose pattern fills in under any ordering).  No factor: every ADMM iteration runs LinOpCg!
+// (LinearSystemSolvers.jl:164-186) for all columns in lockstep on 16-column panels (k_cg_panel.hip) -- the indices and values of P, A and A' are read once per
+// CG iteration for 16 QPs and the launch chain of an iteration is paid once per batch.  Every column keeps its own cg! scalars on the device; the host reads
+// them once per burst of iterations and a column that is done turns into a no-op.  A rho switch costs nothing, the per-row rho scale is a multiplier in the
+// epilogue of A u.  Panels are n and m rows long, without padding rows.
+// =================================================================================================================
+template <typename T> struct CgSharedBatchSolver final : SharedFamilySolver<T> {
+    using B = SharedFamilySolver<T>;
+    using B::device; using B::n; using B::m; using B::count; using B::prof; using B::mem; using B::st; using B::CP; using B::npanel;
+    using B::q; using B::l; using B::u; using B::x; using B::xp; using B::z; using B::zp; using B::y; using B::Ax; using B::Px; using B::Aty;
+    using B::d_active; using B::active; using B::factor_valid; using B::fac_rho; using B::fac_sigma;
+    using B::cat_chk; using B::cat_fac; using B::cat_switch; using B::cat_start; using B::rho_scale; using B::rs_rho; using B::rs_rho1; using B::rs_base;
+    CgPanelArgs<T> a;                      // the matrices, the panels and the scalars of the launches
+    T* w = nullptr;
+    CgPanelState* h_state = nullptr;       // pinned: [0, CP) the scalars after the last burst, [CP, 2 CP) those cg! started from
+    std::vector<int64_t> cg_total;         // per column, over the ADMM iterations of the running solve
+    int last_cg = 0; double eps_pcg = 1e-6; int itr_pcg = 1000;
+    int cat_rhs = 0, cat_it = 0, cat_post = 0;
+
+    CgSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, CgSharedInput&& in, const double* qh, const double* lh, const double* uh)
+        : B(dev, cnt, n_, m_, (int)n_, (int)m_) {
+        layout::CsrHost Ph, Ah, Ath;
+        try {
+            Ph = layout::csc_as_transposed_csr(n, n, in.Pcp, in.Pri, in.Pnz);      // P: CSC == CSR (symmetric, full storage)
+            layout::csc_to_csr_pair(m, n, in.Acp, in.Ari, in.Anz, Ah, Ath);        // rows of A by a counting sort; rows of A' are the columns of A
+        } catch (const std::length_error& ex) { throw QpsError(QPS_ERR_BAD_DIMENSION, ex.what()); }
+        const int64_t pnnz = (int64_t)in.Pnz.size(), annz = (int64_t)in.Anz.size();
+        a.n = (int)n; a.m = (int)m; a.npanel = npanel;
+        a.P = this->upload_csr(Ph); a.A = this->upload_csr(Ah); a.At = this->upload_csr(Ath);
+        a.spr_op = cg_panel_op_spr(pnnz, annz, (int)n);
+        const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
+        q = mem.template dalloc<T>(pn, st); x = mem.template dalloc<T>(pn, st); xp = mem.template dalloc<T>(pn, st); Px = mem.template dalloc<T>(pn, st);
+        Aty = mem.template dalloc<T>(pn, st);
+        l = mem.template dalloc<T>(pm, st); u = mem.template dalloc<T>(pm, st); z = mem.template dalloc<T>(pm, st); zp = mem.template dalloc<T>(pm, st);
+        y = mem.template dalloc<T>(pm, st); Ax = mem.template dalloc<T>(pm, st);   // (dalloc zero-fills: z and y are defined from creation on, as qps_set_shared_warm_start needs)
+        a.xx = mem.template dalloc<T>(pn, st); a.r = mem.template dalloc<T>(pn, st); a.u = mem.template dalloc<T>(pn, st); a.c = mem.template dalloc<T>(pn, st);
+        a.t = mem.template dalloc<T>(pn, st); a.v = mem.template dalloc<T>(pm, st); a.w = w = mem.template dalloc<T>(pm, st);
+        a.part_uc = mem.template dalloc<double>((int64_t)CP * cg_panel_op_blocks((int)n, a.spr_op), st);
+        a.part_rr = mem.template dalloc<double>((int64_t)CP * cg_panel_vec_blocks((int)n), st);
+        a.state = mem.template dalloc<CgPanelState>(2 * (int64_t)CP, st);
+        h_state = mem.template pinned<CgPanelState>(2 * (size_t)CP);
+        this->alloc_check_buffers();
+        a.q = q; a.lo = l; a.hi = u; a.x = x; a.xp = xp; a.z = z; a.zp = zp; a.y = y; a.active = d_active;
+        // algorithmic bytes per launch group, counted as the sparse path counts them: every matrix entry's index and value once per panel, the line it gathers
+        // and the vectors read and written once per column
+        const double sz = sizeof(T), c = CP, np = npanel, ents = (double)(pnnz + 2 * annz);
+        cat_rhs = prof.category("cg shared: rhs, r0 = t - Op(x~) (panels)", np * ents * (sz + 4) + sz * c * (ents + 8.0 * n + 4.0 * m));
+        cat_it = prof.category("cg shared: CG iteration (4 launches)", np * ents * (sz + 4) + sz * c * (ents + 11.0 * n + m));
+        cat_post = prof.category("cg shared: post + update (panels)", np * annz * (sz + 4) + sz * c * (annz + 4.0 * n + 7.0 * m));
+        cat_chk = prof.category("cg shared: check (A x, P x, A'y, norms)", np * ents * (sz + 4) + sz * c * (ents + 8.0 * n + 6.0 * m));
+        this->cat_inf = prof.category("cg shared: infeasibility (deltas, 3 products, sums)", np * ents * (sz + 4) + sz * c * (ents + 10.0 * n + 10.0 * m));
+        cat_fac = prof.category("cg shared: setup (nothing to factor)", 0.0);
+        cat_switch = prof.category("cg shared: rho switch (rho_i only)", sz * 2.0 * m);
+        cat_start = prof.category("cg shared: warm start (A x -> z)", np * annz * (sz + 4) + sz * c * (annz + m));
+        this->update_vectors(qh, lh, uh);
+    }
+    ~CgSharedBatchSolver() override { this->drain(); }
+    void set_equilibration(int passes) override {
+        if (passes > 0) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: equilibration is not supported");
+    }
+    void set_rho_scale(const double* sc) override {
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        if (!sc) {
+            for (T** v : {&rs_rho, &rs_rho1}) { mem.release(*v); *v = nullptr; }
+            rho_scale.clear();
+        } else {
+            if (!rs_rho) rs_rho = mem.template dalloc<T>(m, st);
+            if (!rs_rho1) rs_rho1 = mem.template dalloc<T>(m, st);
+            rho_scale.assign(sc, sc + m);
+        }
+        rs_base = 0;
+    }
+
+  protected:
+    void check_params(const qps_params& p) override {
+        if (p.adptRho) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: adptRho is not supported (the columns run in lockstep on one rho, so the per-problem rule "
+                                                           "cannot run; qps_set_shared_adaptive_rho turns on the family-wide rule)");
+        if (p.polish) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: polish is not supported");
+        if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CG) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: linsys must be QPS_LINSYS_AUTO or QPS_LINSYS_CG");
+        if (!(p.epsPcg >= 0) || !std::isfinite(p.epsPcg)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "CG shared-matrix batch: epsPcg must be finite and >= 0");
+        if (p.numItrPcg < 1) throw QpsError(QPS_ERR_BAD_ARGUMENT, "CG shared-matrix batch: numItrPcg must be >= 1");
+        eps_pcg = p.epsPcg; itr_pcg = p.numItrPcg;
+    }
+    void factor_at_setup(double rho, double sigma, const qps_params&) override { factor_valid = true; fac_rho = rho; fac_sigma = sigma; }   // LinOpCgInit: nothing to factor
+    void begin_solve(int warm, double, double, double) override {
+        for (T* v : {xp, a.xx}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)n, st));   // :38; LinearSystemSolvers.jl:147: x~ starts from zero at every solve
+        if (warm == 0) { for (T* v : {z, zp, y}) HIPC(hipMemsetAsync(v, 0, sizeof(T) * (size_t)CP * (size_t)m, st)); }   // :39-41
+        else HIPC(hipMemsetAsync(zp, 0, sizeof(T) * (size_t)CP * (size_t)m, st));                   // z (mode 1) and y stay
+        if (warm == 2) { ProfScope ps(prof, cat_start, 1); csr_panel<T>(st, a.A, x, (int)n, z, (int)m, npanel); }   // OSQP's warm_start(x, y): z = A x~ without projection
+        this->push_active();
+        cg_total.assign(count, 0);
+        last_cg = 0;
+        a.eps_pcg = eps_pcg; a.max_it = itr_pcg;
+    }
+    void switch_rho(double rho, double) override {
+        if (!rho_scale.empty()) this->push_row_rho(rho);                                            // the operator and the row update read rho_i
+    }
+    void iterate(int lvl, double rho, double sigma, double alpha) override {
+        const bool scaled = !rho_scale.empty();
+        a.rho = (T)rho; a.sigma = (T)sigma; a.alpha = (T)alpha; a.rho_row = scaled ? rs_rho : nullptr; a.rho1_row = scaled ? rs_rho1 : nullptr;
+        {
+            ProfScope ps(prof, cat_rhs, lvl);
+            panel_w<T>(st, z, y, d_active, a.rho_row, a.rho, (int)m, npanel, w);                    // LinearSystemSolvers.jl:176
+            cg_panel_begin<T>(st, a);                                                               // :177-178 and the head of cg!
+        }
+        HIPC(hipMemcpyAsync(h_state + CP, a.state, sizeof(CgPanelState) * (size_t)CP, hipMemcpyDeviceToHost, st));   // read at the first synchronisation
+        // Bursts as CgPlugin::cg sizes them: the first is the previous ADMM iteration's count, every further one what the slowest column's measured contraction
+        // says is left; two at least (a synchronisation costs about one iteration), 64 at most, never past numItrPcg.  A column's arithmetic does not depend
+        // on the burst: an iteration enqueued past its end is a no-op for it.
+        int cur = 0, launched = 0, batch = std::min(std::max(2, std::min(last_cg, 64)), itr_pcg);
+        for (;;) {
+            for (int b = 0; b < batch; ++b) {
+                ProfScope ps(prof, cat_it, lvl);
+                cg_panel_iteration<T>(st, a, cur, b == 0);
+                cur ^= 1;
+            }
+            cg_panel_finish<T>(st, a, cur);
+            launched += batch;
+            HIPC(hipMemcpyAsync(h_state, a.state + (int64_t)cur * CP, sizeof(CgPanelState) * (size_t)CP, hipMemcpyDeviceToHost, st));
+            HIPC(hipStreamSynchronize(st));
+            prof.harvest();
+            int left = 0; bool running = false;
+            for (int b = 0; b < count; ++b) {
+                const CgPanelState &s0 = h_state[CP + b], &s1 = h_state[b];
+                if (!active[b] || s1.done) continue;
+                running = true;
+                const double r0 = std::sqrt(s0.res2), r1 = std::sqrt(s1.res2);
+                int lb = std::max(launched, 1);                                                     // no usable rate: as many again
+                if (r1 > 0 && r0 > r1 && s1.tol > 0 && r1 > s1.tol) lb = (int)std::fmin(64.0, std::ceil(std::log(r1 / s1.tol) / (std::log(r0 / r1) / std::max(1, s1.itn))));
+                left = std::max(left, lb);
+            }
+            if (!running || launched >= itr_pcg) break;
+            batch = std::max(1, std::min(std::min(std::max(left, 2), std::max(launched, 2)), std::min(64, itr_pcg - launched)));
+        }
+        last_cg = 0;
+        for (int b = 0; b < count; ++b) if (active[b]) { cg_total[b] += h_state[b].itn; last_cg = std::max(last_cg, h_state[b].itn); }
+        { ProfScope ps(prof, cat_post, lvl); cg_panel_post<T>(st, a); }                             // :181; SolveQuadraticProgram.jl:56-61
+    }
+    void check_products(const T* xv, const T* yv) override {
+        csr_panel<T>(st, a.A, xv, (int)n, Ax, (int)m, npanel);
+        csr_panel<T>(st, a.P, xv, (int)n, Px, (int)n, npanel);
+        csr_panel<T>(st, a.At, yv, (int)m, Aty, (int)n, npanel);
+    }
+    int64_t column_cg_iterations(int b) override { return b < (int)cg_total.size() ? cg_total[b] : 0; }
+};
+
 }  // namespace
 
 int shared_batch_max_np(int dtype) { return 16 * 512 * (dtype == QPS_F64 ? VecOf<double>::N : VecOf<float>::N); }   // whole-factor explicit inverse: 16384 fp64 / 32768 fp32 (k_trsv.hip)
@@ -767,6 +918,10 @@ BatchSolverBase* make_sparse_shared_batch(int device, int dtype, int count, int6
                                           const double* u) {
     if (dtype == QPS_F64) return new SparseSharedBatchSolver<double>(device, count, n, m, std::move(in), q, l, u);
     return new SparseSharedBatchSolver<float>(device, count, n, m, std::move(in), q, l, u);
+}
+BatchSolverBase* make_cg_shared_batch(int device, int dtype, int count, int64_t n, int64_t m, CgSharedInput&& in, const double* q, const double* l, const double* u) {
+    if (dtype == QPS_F64) return new CgSharedBatchSolver<double>(device, count, n, m, std::move(in), q, l, u);
+    return new CgSharedBatchSolver<float>(device, count, n, m, std::move(in), q, l, u);
 }
 
 }  // namespace qps

@@ -262,6 +262,9 @@ class QuadraticProgramBatch(_Handle):
         _lib.check(_lib.lib().qps_create_dense_batch(self.count, self.n, self.m, _dp(P), _dp(A), _dp(q), _dp(l), _dp(u), dt, device, C.byref(h)))
         self._h = h
 
+    def _extra_params(self, p):
+        """What a subclass adds to the qps_params of ``solve`` (nothing here)."""
+
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
         """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts).  ``mX`` (optional) holds the warm starts."""
@@ -431,6 +434,9 @@ class QuadraticProgramSharedBatch(_Handle):
         an infeasibility flag is left alone.  ``False`` (the default): as without it.  ``polish=True`` of ``solve`` stays refused."""
         _lib.check(_lib.lib().qps_set_shared_polish(self._h, 1 if on else 0), self._h)
 
+    def _extra_params(self, p):
+        """What a subclass adds to the qps_params of ``solve`` (nothing here)."""
+
     def solve(self, mX=None, *, numIterations=5000, ϵAbs=1e-6, ϵRel=1e-6, ρ=1, σ=1e-6, α=1.6, adptΡ=False, fctrΡ=5, numItrConv=25,
               trsvBlock=0, reuseFactor=False, polish=False, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500):
         """Returns (mX [count x n], list of ConvergenceFlag, list of info dicts), as ``QuadraticProgramBatch.solve``.  ``mX`` (optional) holds the warm starts."""
@@ -444,6 +450,7 @@ class QuadraticProgramSharedBatch(_Handle):
         p.trsvBlock, p.reuseFactor = int(trsvBlock), int(bool(reuseFactor))
         p.polish, p.numItrPolish, p.delta, p.epsMinres, p.numItrMinres = int(bool(polish)), int(numItrPolish), float(δ), float(ϵMinres), int(numItrMinres)
         p.linsys = self._linsys
+        self._extra_params(p)
         infos = (QpsInfo * self.count)()
         _lib.check(_lib.lib().qps_solve_batch(self._h, _dp(X), C.byref(p), infos), self._h)
         return X, [ConvergenceFlag(i.convFlag) for i in infos], [i.as_dict() for i in infos]
@@ -464,6 +471,8 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
     ``QuadraticProgram(..., linsys="ldl")`` solve with a fixed ρ (``adptΡ``, ``polish`` and a ``linsys`` other than "auto" / "ldl" are refused with
     QPS_ERR_UNSUPPORTED; ``trsvBlock`` is accepted and without effect).  ``update``, ``solve`` and ``dual`` are those of ``QuadraticProgramSharedBatch``."""
 
+    _create = "qps_create_csc_shared_batch"    # the entry point that takes the CSC arrays
+
     def __init__(self, mP, mA, mQ, mL, mU, *, dtype="f64", device=0):
         if getattr(mP, "ndim", 0) != 2 or getattr(mA, "ndim", 0) != 2:
             raise ValueError("mP and mA must be matrices")
@@ -480,14 +489,35 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
         Acp, Ari, Anz = Ac.indptr.astype(np.int64), Ac.indices.astype(np.int64), np.ascontiguousarray(Ac.data)
         h = C.c_void_p()
         dt = {"f64": QPS_F64, "f32": QPS_F32}[dtype]
-        _lib.check(_lib.lib().qps_create_csc_shared_batch(self.count, self.n, self.m, _ip(Pcp), _ip(Pri), _dp(Pnz), _ip(Acp), _ip(Ari), _dp(Anz),
-                                                          _dp(q), _dp(l), _dp(u), 0, dt, device, C.byref(h)))
+        _lib.check(getattr(_lib.lib(), self._create)(self.count, self.n, self.m, _ip(Pcp), _ip(Pri), _dp(Pnz), _ip(Acp), _ip(Ari), _dp(Anz),
+                                                      _dp(q), _dp(l), _dp(u), 0, dt, device, C.byref(h)))
         self._h = h
 
     def solve(self, mX=None, *, linsys="auto", **kw):
         """As ``QuadraticProgramSharedBatch.solve``; ``linsys`` ("auto" or "ldl": the sparse L D L' either way) goes to the library as it is."""
         self._linsys = {"cholesky": QPS_LINSYS_CHOLESKY, "cg": QPS_LINSYS_CG, "cg_explicit": QPS_LINSYS_CG_EXPLICIT, "ldl": QPS_LINSYS_KKT_LDL, "auto": QPS_LINSYS_AUTO}[linsys]
         return super().solve(mX, **kw)
+
+
+class QuadraticProgramCgSharedBatch(QuadraticProgramSparseSharedBatch):
+    """``count`` QPs on ONE sparse ``mP`` and ONE sparse ``mA`` with the matrix-free CG plugin as their linear system (qps_create_csc_shared_batch_cg): for
+    patterns that fill in under any ordering, which ``QuadraticProgramSparseSharedBatch`` refuses or cannot afford.  Constructor and arrays are those of
+    ``QuadraticProgramSparseSharedBatch``.  Nothing is factorised: every iteration runs one CG per column, all columns in lockstep, the matrices read once per CG
+    iteration for 16 columns.  Every column behaves as a stand-alone ``QuadraticProgram(..., linsys="cg")`` solve (matrix-free) with a fixed ρ and reports its
+    own ``cgIterations``; ``adptΡ``, ``polish`` and a ``linsys`` other than "auto" / "cg" are refused with QPS_ERR_UNSUPPORTED, ``set_equilibration`` with a
+    positive pass count too.  Every other option of ``QuadraticProgramSharedBatch`` works as there; a ρ switch of ``set_adaptive_rho`` costs no factorisation."""
+
+    _create = "qps_create_csc_shared_batch_cg"
+    _cg = (1e-6, 1000)
+
+    def _extra_params(self, p):
+        p.epsPcg, p.numItrPcg = float(self._cg[0]), int(self._cg[1])
+
+    def solve(self, mX=None, *, linsys="auto", ϵPcg=1e-6, numItrPcg=1000, **kw):
+        """As ``QuadraticProgramSharedBatch.solve``; ``ϵPcg`` and ``numItrPcg`` are abstol and maxiter of every column's CG (LinearSystemSolvers.jl:164),
+        ``linsys`` is "auto" or "cg"."""
+        self._cg = (ϵPcg, numItrPcg)
+        return super().solve(mX, linsys=linsys, **kw)
 
 
 # ------------------------------------------------------------------------------------------------------------------
