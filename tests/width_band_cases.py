@@ -37,7 +37,8 @@ P x = d o x + U (U'x).  ``admm_loop`` restates SolveQuadraticProgram.jl:45-71 wi
 Cases ("entry": the first n of a band, ragged inside its 64-pad -- a dispatch off-by-one, the mask of a barely used chunk; "last": 4 real columns
 in the last chunk the instantiation has -- chunk addressing with every chunk live).  NP, B, the instantiations: ``CASES`` / ``PQ_CASES`` below.
 Not covered: fp32 beyond n = 24576 (sweep KC 16 in fp32; its host matrix alone is 4.9 GB, and the fp64 KC 16 cases run the same template code);
-batched passes beyond KC 2; the blocked sweeps (variants 1 and 5).  The polishing pass (MODE 2, apass_kkt: the same bands) has its own table,
+the premultiplied blocked sweep (variant 5).  The batched passes (KC 1 to 8), the batched sweeps and the batched block-phase sweep (variant 1) have
+their own table, tests/batch_band_cases.py, which lists what is still uncovered in a batch (the 1024-thread pass among it).  The polishing pass (MODE 2, apass_kkt: the same bands) has its own table,
 tests/polish_band_cases.py: it needs neither a converged state nor MINRES iteration counts, because its active sets are the signs of a chosen y.
 
 Bounds.  fp64: TOL["f64"] of loop_param_cases.py (ProxQP: the bounds of test_iterates_and_report_match_oracle).  fp32: 100 x the error of the
@@ -211,19 +212,32 @@ def _base_draw():
     return _base
 
 
-class Family:
-    """One member: d, U (weighted), A (m x n, Fortran order, weighted), q, l, u, x0, and for ProxQP b, dd, the explicit start (x0, y0, z0, s0)."""
+def _member_draw(member, n, m):
+    """The draw of member ``member`` of a batch (tests/batch_band_cases.py): the same distributions from that member's own stream, sized to the member."""
+    rng = make_rng(2718, 2 + member)
+    return dict(d=0.5 + rng.random(n), U=rng.standard_normal((n, 8)), A=np.asfortranarray(rng.standard_normal((n, m)).T), q=rng.standard_normal(n),
+                x0=0.3 * rng.standard_normal(n), lo=0.5 + rng.random(m), hi=0.5 + rng.random(m))
 
-    def __init__(self, n, B, m=M_ROWS, weight=WEIGHT, me=None):
-        b = _base_draw()
-        assert n <= N_MAX and m <= M_ROWS and 0 < B < n
-        self.n, self.m, self.B = n, m, B
+
+class Family:
+    """One member: d, U (weighted), A (m x n, Fortran order, weighted), q, l, u, x0, and for ProxQP b, dd, the explicit start (x0, y0, z0, s0).
+    ``member`` (optional, ADMM only): QP number ``member`` of a batch, every array from its own stream, A times ``scale``, l and u times ``tight``; None is the base draw."""
+
+    def __init__(self, n, B, m=M_ROWS, weight=WEIGHT, me=None, member=None, scale=1.0, tight=1.0):
+        b = _base_draw() if member is None else _member_draw(member, n, m)
+        assert (member is not None and me is None) or (n <= N_MAX and m <= M_ROWS and scale == tight == 1.0)
+        assert 0 < B < n
+        self.n, self.m, self.B, self.member, self.scale = n, m, B, member, scale
         wcol = np.where(np.arange(n) >= B, weight, 1.0)
         self.d = b["d"][:n].copy()
         self.U = b["U"][:n] * (wcol / math.sqrt(n))[:, None]
         self.A = np.asfortranarray(b["A"][:m, :n] * (wcol / math.sqrt(n))[None, :])
+        if member is not None:
+            self.A *= scale
         self.q, self.x0 = b["q"][:n].copy(), b["x0"][:n].copy()
         self.l, self.u = -1.05 * b["lo"][:m], 1.05 * b["hi"][:m]
+        if member is not None:
+            self.l, self.u = tight * self.l, tight * self.u
         self.me = me
         if me is not None:                                              # ProxQP: G = [A; C] = the rows of self.A, b = A xf, d = C xf + margin
             xf = b["xf"][:n] / wcol
