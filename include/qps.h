@@ -415,6 +415,33 @@ int32_t qps_create_csc_shared_batch_cg(int64_t count, int64_t n, int64_t m, cons
                                        const int64_t *A_colptr, const int64_t *A_rowval, const double *A_nzval, const double *q, const double *l,
                                        const double *u, int32_t index_base, int32_t dtype, int32_t device, qps_handle *out);
 
+/* New values of P and / or A on a shared-matrix batch handle, in place (OSQP's update_P_A): a linear time-varying MPC, an SQP outer loop or a re-linearised
+ * scenario model keeps the shape and the sparsity pattern and changes the values at every sample.  qps_update_shared_matrices serves the dense handle (P n x n,
+ * ldp; A m x n, lda; column-major as at creation), qps_update_shared_matrices_csc the sparse L D L' and the CG handle (CSC, index base 0 or 1); n, m and count
+ * are the handle's.  A NULL matrix is kept -- for the CSC form the three pointers of a matrix are all NULL or all given -- and with both NULL the call returns
+ * QPS_OK and changes nothing: the factor stays valid.  A given matrix is validated by the code of the creators (leading dimension, NaN / Inf,
+ * issymmetric(mP) with tolerance 0, the CSC field checks), with their codes and messages, before a device is needed.  The arrays are copied.
+ * Pattern (CSC form): the arrays are made canonical as at creation (rows sorted, duplicates summed) and colptr and rowval must then equal the handle's exactly; an
+ * explicit zero is part of the pattern.  Anything else: QPS_ERR_BAD_ARGUMENT, qps_last_error names the matrix and the first column that differs.
+ * Kept: every qps_set_shared_* option with its device buffers, q, l, u, the stored z and y (qps_set_shared_warm_start continues from them across the change),
+ * the ordering, the symbolic factor, every index array and every allocation.  The sparse handles build, at their first update and not before, the position of every
+ * entry of their by-rows copy of A in CSC order (and, while equilibrated, one exponent per stored entry); an update is then one upload of the values as doubles
+ * and one launch per value array.
+ * Stale afterwards: the numeric factor -- the next qps_solve_batch factorises even with reuseFactor = 1, as after qps_set_shared_rho_scale (sparse: the numeric
+ * L D L' on the frozen pattern; CG: nothing to factorise); the dense handle's cached A'A only when A was given (with reuseFactor = 1 a P-only update
+ * re-assembles and runs the Cholesky without the symmetric product), its diag(sqrt(scale)) A is re-formed when a rho scale is set and A was given; and
+ * qps_get_shared_certificate returns zeros until the next solve.
+ * Equilibration on: the exponents are kept, as in OSQP -- the handle stores D P D and E A D with the D, E it has, qps_get_shared_equilibration returns the same
+ * vectors before and after, and a scaling computed from the new matrices is one more qps_set_shared_equilibration(h, passes).  The range check of that call runs on
+ * the new values under the kept exponents before anything is modified (QPS_ERR_UNSUPPORTED).
+ * After any refused call the handle is bit for bit what it was: matrices, factor validity, options and state.  The call returns with the handle's stream idle.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle.  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): the dense entry point on a sparse or CG handle, the CSC entry
+ * point on a dense handle, either on a handle that is not a shared-matrix batch.
+ * Out of scope: a change of pattern or shape, a scaling recomputed inside the update, stand-alone handles, qps_create_dense_batch and ProxQP handles. */
+int32_t qps_update_shared_matrices(qps_handle h, const double *P, int64_t ldp, const double *A, int64_t lda);
+int32_t qps_update_shared_matrices_csc(qps_handle h, const int64_t *P_colptr, const int64_t *P_rowval, const double *P_nzval, const int64_t *A_colptr,
+                                       const int64_t *A_rowval, const double *A_nzval, int32_t index_base);
+
 /* The per-problem loop of RunBenchmarks.jl:88-104 sharded over the devices of ONE process ("one host thread + one stream per device", "work-stealing at
  * chunk boundaries").  `count` independent dense QPs of one shape, arrays stacked as for qps_create_dense_batch; `devices[num_workers]` lists the device of every worker
  * -- one host thread each; a device may be listed more than once (two workers sharing a card).  Every worker repeatedly takes the next range of QPs from a shared

@@ -414,6 +414,32 @@ function SharedBatchUpdate!(sb::SharedBatchHip; mQ::Union{Nothing, Matrix{Float6
     return nothing
 end
 
+# New values of mP and / or mA in place (qps_update_shared_matrices for a SharedBatchCreate handle, qps_update_shared_matrices_csc for SharedBatchCreateSparse /
+# SharedBatchCreateCg): same shape, and for the sparse handles the same stored pattern as at creation (an explicit zero is part of it).  nothing keeps that matrix.
+# Options, q, l, u, the stored z and y, the ordering and the symbolic factor stay; the next SharedBatchSolve! factorises, also with reuseFactor = true.  While
+# equilibrated the handle keeps its D and E; SharedBatchSetEquilibration! again computes them from the new matrices.
+function SharedBatchUpdateMatrices!(sb::SharedBatchHip; mP::Union{Nothing, Matrix{Float64}} = nothing, mA::Union{Nothing, Matrix{Float64}} = nothing)
+    h = sb.h
+    (mP === nothing || size(mP) == (sb.n, sb.n)) || throw(DimensionMismatch("mP must be n x n"))
+    (mA === nothing || size(mA) == (sb.m, sb.n)) || throw(DimensionMismatch("mA must be m x n"))
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve mP mA _check(ccall((:qps_update_shared_matrices, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+                                    h, p(mP), max(sb.n, 1), p(mA), max(sb.m, 1)), h)
+    return nothing
+end
+function SharedBatchUpdateMatricesSparse!(sb::SharedBatchHip; mP::Union{Nothing, SparseMatrixCSC{Float64, Int64}} = nothing,
+    mA::Union{Nothing, SparseMatrixCSC{Float64, Int64}} = nothing)
+    h = sb.h
+    (mP === nothing || size(mP) == (sb.n, sb.n)) || throw(DimensionMismatch("mP must be n x n"))
+    (mA === nothing || size(mA) == (sb.m, sb.n)) || throw(DimensionMismatch("mA must be m x n"))
+    ip(a, f) = a === nothing ? Ptr{Int64}(C_NULL) : pointer(getfield(a, f))
+    dp(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a.nzval)
+    GC.@preserve mP mA _check(ccall((:qps_update_shared_matrices_csc, LIBQPS), Int32,
+        (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32),
+        h, ip(mP, :colptr), ip(mP, :rowval), dp(mP), ip(mA, :colptr), ip(mA, :rowval), dp(mA), Int32(1)), h)   # index_base = 1
+    return nothing
+end
+
 # Per-constraint ρ scale shared by all columns (qps_set_shared_rho_scale): row i runs with ρ_i = ρ vS[i]; vS has m finite, strictly positive entries.
 # nothing goes back to the scalar ρ.  Either way the next SharedBatchSolve! factorises, also with reuseFactor = true.
 function SharedBatchSetRhoScale!(sb::SharedBatchHip, vS::Union{Nothing, Vector{Float64}} = nothing)

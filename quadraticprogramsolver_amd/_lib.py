@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = [
     "qps_create_dense_shared_batch", "qps_update_shared_vectors", "qps_create_csc_shared_batch", "qps_set_shared_rho_scale",
     "qps_set_shared_adaptive_rho", "qps_set_shared_equilibration", "qps_get_shared_equilibration", "qps_set_shared_warm_start", "qps_set_shared_dual",
     "qps_set_shared_infeasibility", "qps_get_shared_certificate", "qps_polish_shared", "qps_set_shared_polish",
-    "qps_create_csc_shared_batch_cg",
+    "qps_create_csc_shared_batch_cg", "qps_update_shared_matrices", "qps_update_shared_matrices_csc",
 ]
 
 QPS_OK = 0
@@ -144,6 +144,8 @@ def lib() -> C.CDLL:
     L.qps_solve_batch.argtypes = [hp, dp, C.POINTER(QpsParams), C.POINTER(QpsInfo)]
     L.qps_create_dense_shared_batch.argtypes = [i64, i64, i64, dp, i64, dp, i64, dp, dp, dp, i32, i32, C.POINTER(hp)]
     L.qps_update_shared_vectors.argtypes = [hp, dp, dp, dp]
+    L.qps_update_shared_matrices.argtypes = [hp, dp, i64, dp, i64]
+    L.qps_update_shared_matrices_csc.argtypes = [hp, ip, ip, dp, ip, ip, dp, i32]
     L.qps_set_shared_rho_scale.argtypes = [hp, dp]
     L.qps_set_shared_adaptive_rho.argtypes = [hp, i32]
     L.qps_set_shared_equilibration.argtypes = [hp, i32]

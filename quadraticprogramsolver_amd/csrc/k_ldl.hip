@@ -625,6 +625,10 @@ template <typename T> struct SparseLdlImpl : SparseLdl<T> {
     int panel_launches_per_solve() const override { return launches_per_solve(); }
     void set_row_rho(const T* rho_row, const T* rho1_row) override { row_rho = rho_row; row_rho1 = rho1_row; }
     void rescale_values(const int* e, int sign) override { scale_entries<T>(st, kval.p, e, sign, kval.n); }
+    void set_values(const double* src, const int* e, int64_t first, int64_t cnt) override {
+        if (first < 0 || cnt < 0 || first + cnt > (int64_t)kval.n) throw QpsError(QPS_ERR_BAD_ARGUMENT, "SparseLdl::set_values: range outside the factor's input array");
+        refresh_values<T>(st, src, nullptr, e, cnt, kval.p + first);
+    }
     template <int SPR> void fwd_panel_launch(int r0, int r1) {
         constexpr int RPB = PS_THREADS / (16 * SPR);
         hipLaunchKernelGGL((k_ldl_fwd_panel<T, SPR>), dim3((unsigned)((r1 - r0 + RPB - 1) / RPB), (unsigned)npanel), dim3(PS_THREADS), 0, st, r0, r1, S.N, S.Ns, S.ldt,

@@ -378,6 +378,18 @@ __global__ __launch_bounds__(256) void k_scale_entries(T* __restrict__ v, const 
     if (i < cnt) v[i] = eq_ldexp(v[i], sign * e[i]);
 }
 
+// dst[k] = 2^e[k] (T) src[map[k]]: one value array of a sparse handle rebuilt from the caller's canonical CSC values (qps_update_shared_matrices_csc).  The value
+// is rounded to T first and scaled afterwards, as creation followed by k_scale_entries does, so both ways give the same bits.  MAP false: dst is in CSC order
+// itself (src[k]); EXP false: no scaling.  map[k] < cnt by construction (a permutation of the positions of one matrix).
+template <typename T, bool MAP, bool EXP>
+__global__ __launch_bounds__(REFRESH_VALUES_THREADS) void k_refresh_values(const double* __restrict__ src, const int* __restrict__ map, const int* __restrict__ e,
+                                                                           int64_t cnt, T* __restrict__ dst) {
+    const int64_t k = (int64_t)blockIdx.x * REFRESH_VALUES_THREADS + threadIdx.x;
+    if (k >= cnt) return;
+    const T v = (T)src[MAP ? (int64_t)map[k] : k];
+    dst[k] = EXP ? eq_ldexp(v, e[k]) : v;
+}
+
 __device__ __forceinline__ double sh_jmax(double a, double b) { return (isnan(a) || isnan(b)) ? (double)NAN : (a > b ? a : b); }
 
 // the decision of k_check_decide for every active column (fixed rho: the proposal stays rho); res: 8 doubles per column
@@ -706,12 +718,21 @@ template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int
     if (cnt <= 0) return;
     hipLaunchKernelGGL((k_scale_entries<T>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, v, e, sign, cnt);
 }
+template <typename T> void refresh_values(hipStream_t st, const double* src, const int* map, const int* e, int64_t cnt, T* dst) {
+    if (cnt <= 0) return;
+    const dim3 grid((unsigned)((cnt + REFRESH_VALUES_THREADS - 1) / REFRESH_VALUES_THREADS)), block(REFRESH_VALUES_THREADS);
+    if (map && e) hipLaunchKernelGGL((k_refresh_values<T, true, true>), grid, block, 0, st, src, map, e, cnt, dst);
+    else if (map) hipLaunchKernelGGL((k_refresh_values<T, true, false>), grid, block, 0, st, src, map, e, cnt, dst);
+    else if (e) hipLaunchKernelGGL((k_refresh_values<T, false, true>), grid, block, 0, st, src, map, e, cnt, dst);
+    else hipLaunchKernelGGL((k_refresh_values<T, false, false>), grid, block, 0, st, src, map, e, cnt, dst);
+}
 
 #define INST(T)                                                                                                                         \
     template void equil_rownorm<T>(hipStream_t, const T*, int, int, const int*, const int*, double*, double*);                          \
     template void scale_two_sided<T>(hipStream_t, T*, int, int, const int*, const int*, int);                                           \
     template void panel_rowscale<T>(hipStream_t, const T*, const int*, int, int, int, T*);                                              \
     template void scale_entries<T>(hipStream_t, T*, const int*, int, int64_t);                                                          \
+    template void refresh_values<T>(hipStream_t, const double*, const int*, const int*, int64_t, T*);                                   \
     template void scale_rows<T>(hipStream_t, const T*, const T*, int, int, T*);                                                         \
     template void panel_w<T>(hipStream_t, const T*, const T*, const int*, const T*, T, int, int, T*);                                   \
     template void shared_panel<T>(hipStream_t, SharedPanelOp, const PanelArgs<T>&);                                                     \

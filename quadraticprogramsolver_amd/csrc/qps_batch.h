@@ -8,6 +8,9 @@
 
 namespace qps {
 
+// One matrix of qps_update_shared_matrices_csc after layout::canonical_csc (0-based, rows sorted, duplicates summed); given == false keeps the handle's matrix
+struct CanonicalCsc { bool given = false; std::vector<int64_t> cp, ri; std::vector<double> nz; };
+
 // What only the shared-matrix batches take (qps_update_shared_vectors, qps_set_shared_*, qps_get_shared_equilibration); arrays validated by the caller.
 struct SharedFamilyOps {
     int family_rho = 0;               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule (one factor, hence one rho to move)
@@ -23,6 +26,12 @@ struct SharedFamilyOps {
     virtual void get_certificate(double* dy, double* dx) = 0;                             // [count][m], [count][n]; either may be NULL
     // qps_polish_shared: x [count][n] (replaced where reports[b].flag == 0), y [count][m] or NULL = the stored y, reports [count] or NULL; finite arrays
     virtual void polish(double* x, const double* y, const qps_params& p, qps_polish_report* reports) = 0;
+    // qps_update_shared_matrices / qps_update_shared_matrices_csc: new values on the handle's pattern, everything else kept (options, q, l, u, z, y, analysis,
+    // allocations); the numeric factor goes stale.  A path implements the form it was created from; the other form is refused with QPS_ERR_UNSUPPORTED before the
+    // arrays are looked at (takes_csc() tells qps_capi.hip which).  A refused call leaves the handle bit for bit what it was; a returning call leaves the stream idle.
+    virtual bool takes_csc() const = 0;
+    virtual void update_matrices(const double* P, int64_t ldp, const double* A, int64_t lda) = 0;   // column-major, NULL keeps that matrix
+    virtual void update_matrices_csc(const CanonicalCsc& P, const CanonicalCsc& A) = 0;             // pattern compared with the handle's, entry for entry
 };
 
 struct BatchSolverBase {

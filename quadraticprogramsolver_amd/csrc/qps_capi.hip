@@ -136,9 +136,37 @@ int check_vectors(int64_t n, int64_t m, const double* q, const double* l, const 
     if (m > 0 && (!all_finite(l, count * m, true) || !all_finite(u, count * m, true))) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "l/u contain NaN");
     return QPS_OK;
 }
-int fail_asymmetric(int64_t column) {                                                    // SolveQuadraticProgram.m:166-168
+int fail_asymmetric(int64_t column, Handle* h = nullptr) {                               // SolveQuadraticProgram.m:166-168
     char b[160]; snprintf(b, sizeof b, "The matrix mP must be a symmetric positive definite matrix (asymmetric entry in column %lld)", (long long)column);
-    return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, b);
+    return fail_with(h, QPS_ERR_BAD_ARGUMENT, b);
+}
+// The matrix tests of a dense problem shape, shared by the creators and qps_update_shared_matrices (there a NULL matrix is kept and not tested; h: whose error text)
+int check_dense_ld(int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda, Handle* h = nullptr) {
+    if ((P && ldp < n) || (A && m > 0 && lda < m)) return fail_with(h, QPS_ERR_BAD_DIMENSION, "leading dimension smaller than the row count");
+    return QPS_OK;
+}
+int check_dense_finite(int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda, Handle* h = nullptr) {
+    if (P && !all_finite_matrix(P, n, n, ldp)) return fail_with(h, QPS_ERR_NOT_FINITE, "P contains NaN/Inf");
+    if (A && m > 0 && !all_finite_matrix(A, m, n, lda)) return fail_with(h, QPS_ERR_NOT_FINITE, "A contains NaN/Inf");
+    return QPS_OK;
+}
+int check_dense_symmetry(int64_t n, const double* P, int64_t ldp, Handle* h = nullptr) {
+    const int64_t bad = P ? dense_asymmetry(P, n, ldp) : -1;
+    return bad >= 0 ? fail_asymmetric(bad, h) : QPS_OK;
+}
+// ... and of a CSC problem shape (layout::validate_csc, layout::csc_asymmetry); a matrix whose colptr is NULL is kept and not tested
+int check_csc_matrices(int64_t n, int64_t m, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const int64_t* Acp, const int64_t* Ari, const double* Anz,
+                       int index_base, Handle* h = nullptr) {
+    std::string why;
+    int vc = Pcp ? layout::validate_csc(n, n, Pcp, Pri, Pnz, index_base, "P", &why) : 0;
+    if (vc == 0 && Acp) vc = layout::validate_csc(m, n, Acp, Ari, Anz, index_base, "A", &why);
+    return vc != 0 ? fail_with(h, vc, why) : QPS_OK;
+}
+int check_csc_symmetry(int64_t n, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, int index_base, Handle* h = nullptr) {
+    if (!Pcp) return QPS_OK;
+    int64_t bad = -1;
+    if (const int rc = guarded(h, [&] { bad = layout::csc_asymmetry(n, Pcp, Pri, Pnz, index_base); })) return rc;
+    return bad >= 0 ? fail_asymmetric(bad, h) : QPS_OK;
 }
 // One dense problem shape: column-major P (ld ldp) and A (ld lda), `count` columns of q / l / u
 int check_dense_shape(int64_t n, int64_t m, const double* P, int64_t ldp, const double* A, int64_t lda, const double* q, const double* l, const double* u, int dtype,
@@ -146,13 +174,11 @@ int check_dense_shape(int64_t n, int64_t m, const double* P, int64_t ldp, const 
     if (const int rc = check_dims(n, m)) return rc;
     if (n > (1 << 20) || m > (1 << 24)) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "dense problem too large");
     if (!P || !q || (m > 0 && (!A || !l || !u))) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "NULL problem array");
-    if (ldp < n || (m > 0 && lda < m)) return fail_with(nullptr, QPS_ERR_BAD_DIMENSION, "leading dimension smaller than the row count");
+    if (const int rc = check_dense_ld(n, m, P, ldp, A, lda)) return rc;
     if (const int rc = check_dtype(dtype)) return rc;
-    if (!all_finite_matrix(P, n, n, ldp)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "P contains NaN/Inf");
-    if (m > 0 && !all_finite_matrix(A, m, n, lda)) return fail_with(nullptr, QPS_ERR_NOT_FINITE, "A contains NaN/Inf");
+    if (const int rc = check_dense_finite(n, m, P, ldp, A, lda)) return rc;
     if (const int rc = check_vectors(n, m, q, l, u, count)) return rc;
-    const int64_t bad = dense_asymmetry(P, n, ldp);
-    return bad >= 0 ? fail_asymmetric(bad) : QPS_OK;
+    return check_dense_symmetry(n, P, ldp);
 }
 // One CSC problem shape; colptr / rowval / nzval of both matrices by plain host code shared with the CPU tests (spmv_layout.cpp)
 int check_csc_shape(int64_t n, int64_t m, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const int64_t* Acp, const int64_t* Ari, const double* Anz,
@@ -161,14 +187,9 @@ int check_csc_shape(int64_t n, int64_t m, const int64_t* Pcp, const int64_t* Pri
     if (!Pcp || !q || !Acp || (m > 0 && (!l || !u))) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "NULL problem array");
     if (index_base != 0 && index_base != 1) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "index_base must be 0 or 1");
     if (const int rc = check_dtype(dtype)) return rc;
-    std::string why;
-    int vc = layout::validate_csc(n, n, Pcp, Pri, Pnz, index_base, "P", &why);
-    if (vc == 0) vc = layout::validate_csc(m, n, Acp, Ari, Anz, index_base, "A", &why);
-    if (vc != 0) return fail_with(nullptr, vc, why);
+    if (const int rc = check_csc_matrices(n, m, Pcp, Pri, Pnz, Acp, Ari, Anz, index_base)) return rc;
     if (const int rc = check_vectors(n, m, q, l, u, count)) return rc;
-    int64_t bad = -1;
-    if (const int rc = guarded(nullptr, [&] { bad = layout::csc_asymmetry(n, Pcp, Pri, Pnz, index_base); })) return rc;
-    return bad >= 0 ? fail_asymmetric(bad) : QPS_OK;
+    return check_csc_symmetry(n, Pcp, Pri, Pnz, index_base);
 }
 // CSC (rows x n) -> column-major dense with leading dimension max(rows, 1), duplicates summed; rows == 0: colptr is not read
 std::vector<double> densify_csc(const int64_t* cp, const int64_t* ri, const double* nz, int64_t rows, int64_t n, int index_base) {
@@ -408,6 +429,40 @@ QPS_API int32_t qps_update_shared_vectors(qps_handle hh, const double* q, const 
     SharedFamilyOps* fam = shared_family_of(h);
     if (!fam) return fail_with(h, QPS_ERR_BAD_ARGUMENT, other);
     return guarded(h, [&] { fam->update_vectors(q, l, u); });
+}
+
+QPS_API int32_t qps_update_shared_matrices(qps_handle hh, const double* P, int64_t ldp, const double* A, int64_t lda) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_update_shared_matrices", "take new matrices on the analysis they keep", &rc);
+    if (!fam) return rc;
+    if (fam->takes_csc()) return guarded(h, [&] { fam->update_matrices(nullptr, 0, nullptr, 0); });   // the path words its own refusal
+    if (const int c = check_dense_ld(h->n, h->m, P, ldp, A, lda, h)) return c;
+    if (const int c = check_dense_finite(h->n, h->m, P, ldp, A, lda, h)) return c;
+    if (const int c = check_dense_symmetry(h->n, P, ldp, h)) return c;
+    return guarded(h, [&] { fam->update_matrices(P, ldp, A, lda); });
+}
+
+QPS_API int32_t qps_update_shared_matrices_csc(qps_handle hh, const int64_t* Pcp, const int64_t* Pri, const double* Pnz, const int64_t* Acp, const int64_t* Ari,
+                                               const double* Anz, int32_t index_base) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_update_shared_matrices_csc", "take new matrices on the analysis they keep", &rc);
+    if (!fam) return rc;
+    CanonicalCsc Pc, Ac;
+    if (!fam->takes_csc()) return guarded(h, [&] { fam->update_matrices_csc(Pc, Ac); });              // the path words its own refusal
+    const bool anyP = Pcp || Pri || Pnz, anyA = Acp || Ari || Anz;
+    if ((anyP && !(Pcp && Pri && Pnz)) || (anyA && !(Acp && Ari && Anz)))
+        return fail_with(h, QPS_ERR_BAD_ARGUMENT, std::string("qps_update_shared_matrices_csc: colptr, rowval and nzval of ") + (anyP && !(Pcp && Pri && Pnz) ? "P" : "A") +
+                                                      " must be all NULL (the matrix is kept) or all given");
+    if (index_base != 0 && index_base != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "index_base must be 0 or 1");
+    if (const int c = check_csc_matrices(h->n, h->m, Pcp, Pri, Pnz, Acp, Ari, Anz, index_base, h)) return c;
+    if (const int c = check_csc_symmetry(h->n, Pcp, Pri, Pnz, index_base, h)) return c;
+    return guarded(h, [&] {
+        if (anyP) { layout::canonical_csc(h->n, Pcp, Pri, Pnz, index_base, Pc.cp, Pc.ri, Pc.nz); Pc.given = true; }
+        if (anyA) { layout::canonical_csc(h->n, Acp, Ari, Anz, index_base, Ac.cp, Ac.ri, Ac.nz); Ac.given = true; }
+        fam->update_matrices_csc(Pc, Ac);
+    });
 }
 
 QPS_API int32_t qps_set_shared_rho_scale(qps_handle hh, const double* scale) {

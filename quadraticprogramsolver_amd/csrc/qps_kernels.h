@@ -177,6 +177,10 @@ void equil_update(hipStream_t st, int len, const double* a, const double* b, int
 template <typename T> void scale_two_sided(hipStream_t st, T* M, int rows, int cols, const int* kr, const int* kc, int sign);
 template <typename T> void panel_rowscale(hipStream_t st, const T* src, const int* k, int sign, int rowsP, int npanel, T* dst);
 template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int sign, int64_t cnt);
+// refresh_values: dst[k] = 2^e[k] (T) src[map[k]] for k < cnt -- a value array of a sparse shared-matrix batch rebuilt from canonical CSC values in double
+// (qps_update_shared_matrices_csc); rounded to T first, scaled afterwards.  map == NULL: src[k]; e == NULL: no scaling.  One entry per lane.
+constexpr int REFRESH_VALUES_THREADS = 256;
+template <typename T> void refresh_values(hipStream_t st, const double* src, const int* map, const int* e, int64_t cnt, T* dst);
 // out[panel][r][16] = sum_k M[r][k] B[panel][k][16] for a plain CSR matrix (k_csr_panel.hip): the check's products of the sparse shared batch.  One 16-lane
 // row per (matrix row, panel), spr strips of it for long rows (csr_panel_spr: from the mean row length), fixed summation order, no atomics.
 // rowsB / rowsOut: rows per panel of B / out.

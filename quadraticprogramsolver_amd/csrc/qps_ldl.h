@@ -49,6 +49,10 @@ template <typename T> struct SparseLdl {
     // order -- is multiplied by 2^(sign e[k]) in place on the handle's stream (e: device array, one exponent per entry, built by the caller from the pattern).
     // The pattern, the ordering and the symbolic factor stay; the numeric factor is stale until the next factorize().
     virtual void rescale_values(const int* e, int sign) = 0;
+    // New values on the frozen pattern (qps_update_shared_matrices_csc): entries [first, first + cnt) of the factor's input array -- P's values from 0, A's from
+    // nnz(P), the caller's CSC order -- become 2^e[k] (T) src[k] (src: device doubles, e: device exponents or nullptr), on the handle's stream.  The next
+    // factorize() is the pattern-reusing re-factorisation on them; until then the numeric factor is stale.
+    virtual void set_values(const double* src, const int* e, int64_t first, int64_t cnt) = 0;
     virtual const LdlSymbolic& symbolic() const = 0;
     virtual int launches_per_solve() const = 0;
     virtual double bytes_per_solve() const = 0;

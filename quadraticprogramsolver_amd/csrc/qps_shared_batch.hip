@@ -17,12 +17,30 @@ namespace qps {
 namespace {
 
 // the range check of the equilibration: every non-zero scaled matrix entry has to stay a normal number of the handle's type
-template <typename T> inline void equil_check_range(double hi, double lo) {
+template <typename T> inline void equil_check_range(double hi, double lo, const char* fn = "qps_set_shared_equilibration") {
     if (hi > (double)std::numeric_limits<T>::max() || lo < (double)std::numeric_limits<T>::min()) {
         char b[256];
-        snprintf(b, sizeof b, "qps_set_shared_equilibration: a scaled matrix entry would leave the normal range of the handle's type (largest %.3g, smallest non-zero %.3g, "
-                              "range %.3g .. %.3g); the handle is unchanged", hi, lo, (double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max());
+        snprintf(b, sizeof b, "%s: a scaled matrix entry would leave the normal range of the handle's type (largest %.3g, smallest non-zero %.3g, "
+                              "range %.3g .. %.3g); the handle is unchanged", fn, hi, lo, (double)std::numeric_limits<T>::min(), (double)std::numeric_limits<T>::max());
         throw QpsError(QPS_ERR_UNSUPPORTED, b);
+    }
+}
+// |(T) v| 2^e of one new matrix entry under a kept exponent, into the running range (qps_update_shared_matrices*: checked on the host before anything is modified)
+template <typename T> inline void equil_range_add(double v, int e, double& hi, double& lo) {
+    const double a = std::ldexp(std::fabs((double)(T)v), e);
+    hi = std::fmax(hi, a);
+    if (a > 0) lo = std::fmin(lo, a);
+}
+// qps_update_shared_matrices_csc: the canonical pattern of a given matrix has to be the handle's, entry for entry (an explicit zero is part of it)
+inline void require_same_pattern(const char* name, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const CanonicalCsc& c) {
+    if (!c.given) return;
+    for (int64_t j = 0; j < ncols; ++j) {
+        const int64_t a0 = cp[(size_t)j], a1 = cp[(size_t)j + 1], b0 = c.cp[(size_t)j], b1 = c.cp[(size_t)j + 1];
+        if (a1 - a0 == b1 - b0 && std::equal(ri.begin() + a0, ri.begin() + a1, c.ri.begin() + b0)) continue;
+        char b[256];
+        snprintf(b, sizeof b, "qps_update_shared_matrices_csc: the sparsity pattern of %s differs from the handle's (first in column %lld, 0-based; %lld stored entries there "
+                              "against %lld); the handle is unchanged", name, (long long)j, (long long)(b1 - b0), (long long)(a1 - a0));
+        throw QpsError(QPS_ERR_BAD_ARGUMENT, b);
     }
 }
 
@@ -389,6 +407,7 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
     T *A = nullptr, *At = nullptr, *P = nullptr, *PI = nullptr, *AA = nullptr, *M = nullptr, *S = nullptr, *tmp = nullptr, *dinv = nullptr;
     T *xx = nullptr, *tt = nullptr, *yv = nullptr, *w = nullptr;
     int* fail = nullptr; bool have_AA = false;
+    bool pi_stale = false;   // qps_update_shared_matrices replaced P alone: PI = P + sigma I is rebuilt at the next factorisation, the cached A'A is not
     int cat_atw = 0, cat_fwd = 0, cat_bwd = 0, cat_pass = 0;
     // The per-row rho scale here: Ws = diag(sqrt(s_i)) A (MP x NP) stands in for A when A'A is formed, so M = PI + rho Ws'Ws comes out of the same symmetric
     // product and a change of the base rho alone only re-assembles.  Equilibration: At holds D A' E beside D P D and E A D.
@@ -428,6 +447,45 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         upload_matrix_panels<T>(st, device, Ah, lda, (int)m, (int)n, A, NP);
         transpose_rowmajor<T>(st, A, NP, MP, NP, At, MP);   // row-major A': every product of the loop is "row-major matrix x panel"
         this->update_vectors(qh, lh, uh);
+    }
+    bool takes_csc() const override { return false; }
+    void update_matrices_csc(const CanonicalCsc&, const CanonicalCsc&) override {
+        throw QpsError(QPS_ERR_UNSUPPORTED, "qps_update_shared_matrices_csc: a dense shared-matrix batch takes its matrices through qps_update_shared_matrices");
+    }
+    // New P and / or A (column-major, validated by the caller) into the storage of the old ones, scaled by the kept exponents while the equilibration is on; q, l,
+    // u, z, y, every option and every allocation stay.  The range of the scaled entries is checked on the host before the first upload.
+    void update_matrices(const double* Ph, int64_t ldp, const double* Ah, int64_t lda) override {
+        if (!Ph && !Ah) return;
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        if (kd) {
+            const int nt = host_threads();
+            std::vector<double> his((size_t)nt, 0.0), los((size_t)nt, INFINITY);
+            host_parallel(n, 64, [&](int t, int64_t j0, int64_t j1) {
+                double hi = 0, lo = INFINITY;
+                for (int64_t j = j0; j < j1; ++j) {
+                    for (int64_t i = 0; Ph && i < n; ++i) equil_range_add<T>(Ph[i + j * ldp], eq_kd[i] + eq_kd[j], hi, lo);
+                    for (int64_t i = 0; Ah && i < m; ++i) equil_range_add<T>(Ah[i + j * lda], eq_ke[i] + eq_kd[j], hi, lo);
+                }
+                his[t] = hi; los[t] = lo;
+            });
+            equil_check_range<T>(*std::max_element(his.begin(), his.end()), *std::min_element(los.begin(), los.end()), "qps_update_shared_matrices");
+        }
+        if (Ph) {
+            upload_matrix_panels<T>(st, device, Ph, ldp, (int)n, (int)n, P, NP);
+            if (kd) scale_two_sided<T>(st, P, NP, NP, kd, kd, 1);
+            pi_stale = true;
+        }
+        if (Ah) {
+            upload_matrix_panels<T>(st, device, Ah, lda, (int)m, (int)n, A, NP);
+            transpose_rowmajor<T>(st, A, NP, MP, NP, At, MP);
+            if (kd) { scale_two_sided<T>(st, A, MP, NP, ke, kd, 1); scale_two_sided<T>(st, At, NP, MP, kd, ke, 1); }
+            if (Ws) scale_rows<T>(st, A, rs_sqrt, MP, NP, Ws);         // the per-row rho scale reads the new A
+            have_AA = false;                                           // the cached product belongs to the previous A
+        }
+        HIPC(hipStreamSynchronize(st));
+        factor_valid = false;                                          // the next solve factorises, also with reuseFactor
+        this->last_conv.clear();
     }
     // the matrices and every vector the handle keeps between calls, in place: *= 2^(+-k) by the exponents in kd / ke
     void apply_equilibration(int sign) {
@@ -507,8 +565,8 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
         const DenseChol<T> c{st, (int)n, NP, MP, P, rho_scale.empty() ? A : Ws, PI, AA, M, S, tmp, dinv, fail};   // A'A, or A' diag(s) A = Ws'Ws
         factor_valid = false;
         HIPC(hipMemsetAsync(fail, 0, sizeof(int) * 4, st));
-        c.form(sigma, rho, rebuild, rebuild);
-        have_AA = true;
+        c.form(sigma, rho, rebuild || pi_stale, rebuild);
+        have_AA = true; pi_stale = false;
         c.factor(nb);
         char ctx[128]; snprintf(ctx, sizeof ctx, "rho=%g, sigma=%g; factorisation #%d of this handle", rho, sigma, ++num_factorizations);
         c.check("P + sigma I + rho A'A", ctx, h_int);
@@ -591,6 +649,9 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
     // Equilibration: the exponents come from the host copy of the canonical CSC arrays (values rounded to T); while it is on, the factor's value array and the
     // three CSR value arrays of the check hold the scaled entries.  Ordering, symbolic factor and every index array stay as they are.
     std::vector<int64_t> hPcp, hPri, hAcp, hAri; std::vector<double> hPnz, hAnz;
+    // qps_update_shared_matrices_csc, from its first call on: the staging of the canonical values (nnz(P) + nnz(A) doubles), the position of every entry of the
+    // by-rows copy of A in CSC order, and -- while the equilibration is on -- the exponent of every entry of the four value arrays
+    double* upd_src = nullptr; int *upd_map = nullptr, *upd_e = nullptr;
     LdlPanelState<T> s; bool rhs_ready = false;   // the running solve
 
     SparseSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, SparseSharedInput&& in, const double* qh, const double* lh, const double* uh)
@@ -631,12 +692,61 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         this->update_vectors(qh, lh, uh);
     }
     ~SparseSharedBatchSolver() override { this->drain(); }   // before ldl and its device buffers go
-    // every value array and every vector the handle keeps between calls, in place: *= 2^(+-k) by the host exponents hd / he (device copies in kd / ke)
-    void apply_equilibration(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
+    bool takes_csc() const override { return true; }
+    void update_matrices(const double*, int64_t, const double*, int64_t) override {
+        throw QpsError(QPS_ERR_UNSUPPORTED, "qps_update_shared_matrices: a sparse shared-matrix batch takes its matrices through qps_update_shared_matrices_csc");
+    }
+    // New values on the frozen pattern: one upload of the canonical values as doubles, then one launch per value array (the CSR copies P, A, A' and the factor's
+    // [P; A]) that rounds, permutes and scales.  upd_src, upd_map and upd_e are built at the first update and kept; upd_e goes whenever the scaling changes.
+    void update_matrices_csc(const CanonicalCsc& Pc, const CanonicalCsc& Ac) override {
+        if (!Pc.given && !Ac.given) return;
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        require_same_pattern("P", n, hPcp, hPri, Pc);
+        require_same_pattern("A", n, hAcp, hAri, Ac);
+        const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
+        if (kd) {                                                  // the kept exponents on the new values, before anything is modified
+            double hi = 0, lo = INFINITY;
+            for (int64_t j = 0; j < n; ++j) {
+                for (int64_t k = hPcp[j]; Pc.given && k < hPcp[j + 1]; ++k) equil_range_add<T>(Pc.nz[k], eq_kd[hPri[k]] + eq_kd[j], hi, lo);
+                for (int64_t k = hAcp[j]; Ac.given && k < hAcp[j + 1]; ++k) equil_range_add<T>(Ac.nz[k], eq_ke[hAri[k]] + eq_kd[j], hi, lo);
+            }
+            equil_check_range<T>(hi, lo, "qps_update_shared_matrices_csc");
+        }
+        if (!upd_src) upd_src = mem.template dalloc<double>(pnnz + annz, st);
+        if (!upd_map) {
+            const std::vector<int> map = layout::csc_rows_position_map(m, n, hAcp, hAri);
+            upd_map = mem.template dalloc<int>(annz, st);
+            if (annz > 0) up->copy(upd_map, map.data(), sizeof(int) * (size_t)annz);
+        }
+        if (kd && !upd_e) {
+            const std::vector<int> e = entry_exponents(eq_kd, eq_ke);
+            upd_e = mem.template dalloc<int>((int64_t)e.size(), st);
+            if (!e.empty()) up->copy(upd_e, e.data(), sizeof(int) * e.size());
+        }
+        const int *eK = upd_e, *eP = upd_e ? upd_e + pnnz + annz : nullptr, *eA = upd_e ? eP + pnnz : nullptr, *eAt = upd_e ? eA + annz : nullptr;
+        if (Pc.given && pnnz > 0) {
+            up->copy(upd_src, Pc.nz.data(), sizeof(double) * (size_t)pnnz);
+            refresh_values<T>(st, upd_src, nullptr, eP, pnnz, const_cast<T*>(P.va));
+            ldl->set_values(upd_src, eK, 0, pnnz);
+        }
+        if (Ac.given && annz > 0) {
+            up->copy(upd_src + pnnz, Ac.nz.data(), sizeof(double) * (size_t)annz);
+            refresh_values<T>(st, upd_src + pnnz, upd_map, eA, annz, const_cast<T*>(A.va));
+            refresh_values<T>(st, upd_src + pnnz, nullptr, eAt, annz, const_cast<T*>(At.va));
+            ldl->set_values(upd_src + pnnz, eK ? eK + pnnz : nullptr, pnnz, annz);
+        }
+        HIPC(hipStreamSynchronize(st));
+        if (Pc.given) hPnz = Pc.nz;                                // what a later qps_set_shared_equilibration computes its exponents from
+        if (Ac.given) hAnz = Ac.nz;
+        factor_valid = false;                                      // the next solve runs the numeric factorisation on the frozen pattern, also with reuseFactor
+        this->last_conv.clear();
+    }
+    // one exponent per entry, in the order of each value array: the factor's [P; A] in CSC order, then the CSR copies P, A, A'
+    std::vector<int> entry_exponents(const std::vector<int>& hd, const std::vector<int>& he) const {
         const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
         layout::CsrHost Ph = layout::csc_as_transposed_csr(n, n, hPcp, hPri, hPnz), Ah, Ath;
         layout::csc_to_csr_pair(m, n, hAcp, hAri, hAnz, Ah, Ath);
-        // one exponent per entry, in the order of each value array: the factor's [P; A] in CSC order, then the CSR copies P, A, A'
         std::vector<int> e((size_t)(2 * pnnz + 3 * annz));
         int* eK = e.data(); int *eP = eK + pnnz + annz, *eA = eP + pnnz, *eAt = eA + annz;
         for (int64_t j = 0; j < n; ++j) {
@@ -646,15 +756,25 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         for (int r = 0; r < Ph.nrows; ++r) for (int k = Ph.rp[r]; k < Ph.rp[r + 1]; ++k) eP[k] = hd[r] + hd[Ph.ci[k]];
         for (int r = 0; r < Ah.nrows; ++r) for (int k = Ah.rp[r]; k < Ah.rp[r + 1]; ++k) eA[k] = he[r] + hd[Ah.ci[k]];
         for (int r = 0; r < Ath.nrows; ++r) for (int k = Ath.rp[r]; k < Ath.rp[r + 1]; ++k) eAt[k] = hd[r] + he[Ath.ci[k]];
+        return e;
+    }
+    // every value array, in place: *= 2^(+-k) by the host exponents hd / he (the vectors the handle keeps are not touched)
+    void scale_matrix_values(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
+        const int64_t pnnz = (int64_t)hPnz.size(), annz = (int64_t)hAnz.size();
+        const std::vector<int> e = entry_exponents(hd, he);
         int* de = mem.template dalloc<int>((int64_t)e.size(), st);
         if (!e.empty()) up->copy(de, e.data(), sizeof(int) * e.size());
         ldl->rescale_values(de, sign);
         scale_entries<T>(st, const_cast<T*>(P.va), de + pnnz + annz, sign, pnnz);
         scale_entries<T>(st, const_cast<T*>(A.va), de + 2 * pnnz + annz, sign, annz);
         scale_entries<T>(st, const_cast<T*>(At.va), de + 2 * pnnz + 2 * annz, sign, annz);
-        this->rescale_kept_vectors(sign);
         HIPC(hipStreamSynchronize(st));
         mem.release(de);
+    }
+    // every value array and every vector the handle keeps between calls, in place (device copies of the exponents in kd / ke)
+    void apply_equilibration(int sign, const std::vector<int>& hd, const std::vector<int>& he) {
+        this->rescale_kept_vectors(sign);
+        scale_matrix_values(sign, hd, he);
     }
     void set_equilibration(int passes) override {
         HIPC(hipSetDevice(device));
@@ -690,6 +810,7 @@ template <typename T> struct SparseSharedBatchSolver final : SharedFamilySolver<
         }
         if (kd) apply_equilibration(-1, eq_kd, eq_ke);             // the caller's values again, bit for bit
         mem.release(kd); mem.release(ke); kd = ke = nullptr;
+        mem.release(upd_e); upd_e = nullptr;                       // the per-entry exponents of qps_update_shared_matrices_csc belong to the previous scaling
         eq_kd = hd; eq_ke = he;
         if (passes > 0) {
             kd = mem.template dalloc<int>(n, st); ke = mem.template dalloc<int>(m, st);
@@ -775,6 +896,9 @@ template <typename T> struct CgSharedBatchSolver final : SharedFamilySolver<T> {
     std::vector<int64_t> cg_total;         // per column, over the ADMM iterations of the running solve
     int last_cg = 0; double eps_pcg = 1e-6; int itr_pcg = 1000;
     int cat_rhs = 0, cat_it = 0, cat_post = 0;
+    // qps_update_shared_matrices_csc: the canonical pattern the handle was created on (the values are not kept), and from the first update on the staging of the
+    // new values and the position of every entry of the by-rows copy of A in CSC order
+    std::vector<int64_t> hPcp, hPri, hAcp, hAri; double* upd_src = nullptr; int* upd_map = nullptr;
 
     CgSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, CgSharedInput&& in, const double* qh, const double* lh, const double* uh)
         : B(dev, cnt, n_, m_, (int)n_, (int)m_) {
@@ -787,6 +911,7 @@ template <typename T> struct CgSharedBatchSolver final : SharedFamilySolver<T> {
         a.n = (int)n; a.m = (int)m; a.npanel = npanel;
         a.P = this->upload_csr(Ph); a.A = this->upload_csr(Ah); a.At = this->upload_csr(Ath);
         a.spr_op = cg_panel_op_spr(pnnz, annz, (int)n);
+        hPcp = std::move(in.Pcp); hPri = std::move(in.Pri); hAcp = std::move(in.Acp); hAri = std::move(in.Ari);
         const int64_t pn = (int64_t)CP * n, pm = (int64_t)CP * m;
         q = mem.template dalloc<T>(pn, st); x = mem.template dalloc<T>(pn, st); xp = mem.template dalloc<T>(pn, st); Px = mem.template dalloc<T>(pn, st);
         Aty = mem.template dalloc<T>(pn, st);
@@ -814,6 +939,37 @@ template <typename T> struct CgSharedBatchSolver final : SharedFamilySolver<T> {
         this->update_vectors(qh, lh, uh);
     }
     ~CgSharedBatchSolver() override { this->drain(); }
+    bool takes_csc() const override { return true; }
+    void update_matrices(const double*, int64_t, const double*, int64_t) override {
+        throw QpsError(QPS_ERR_UNSUPPORTED, "qps_update_shared_matrices: a CG shared-matrix batch takes its matrices through qps_update_shared_matrices_csc");
+    }
+    // New values on the frozen pattern of the three CSR copies the operator and the check read; nothing is factorised on this path
+    void update_matrices_csc(const CanonicalCsc& Pc, const CanonicalCsc& Ac) override {
+        if (!Pc.given && !Ac.given) return;
+        HIPC(hipSetDevice(device));
+        HIPC(hipStreamSynchronize(st));
+        require_same_pattern("P", n, hPcp, hPri, Pc);
+        require_same_pattern("A", n, hAcp, hAri, Ac);
+        const int64_t pnnz = (int64_t)hPri.size(), annz = (int64_t)hAri.size();
+        if (!upd_src) upd_src = mem.template dalloc<double>(pnnz + annz, st);
+        if (!upd_map) {
+            const std::vector<int> map = layout::csc_rows_position_map(m, n, hAcp, hAri);
+            upd_map = mem.template dalloc<int>(annz, st);
+            if (annz > 0) this->up->copy(upd_map, map.data(), sizeof(int) * (size_t)annz);
+        }
+        if (Pc.given && pnnz > 0) {
+            this->up->copy(upd_src, Pc.nz.data(), sizeof(double) * (size_t)pnnz);
+            refresh_values<T>(st, upd_src, nullptr, nullptr, pnnz, const_cast<T*>(a.P.va));
+        }
+        if (Ac.given && annz > 0) {
+            this->up->copy(upd_src + pnnz, Ac.nz.data(), sizeof(double) * (size_t)annz);
+            refresh_values<T>(st, upd_src + pnnz, upd_map, nullptr, annz, const_cast<T*>(a.A.va));
+            refresh_values<T>(st, upd_src + pnnz, nullptr, nullptr, annz, const_cast<T*>(a.At.va));
+        }
+        HIPC(hipStreamSynchronize(st));
+        factor_valid = false;
+        this->last_conv.clear();
+    }
     void set_equilibration(int passes) override {
         if (passes > 0) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: equilibration is not supported");
     }

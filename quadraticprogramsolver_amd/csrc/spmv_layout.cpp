@@ -94,6 +94,16 @@ void csc_to_csr_pair(int64_t nrows, int64_t ncols, const std::vector<int64_t>& c
         }
 }
 
+std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri) {
+    const int64_t nnz = cp[(size_t)ncols];
+    if (nnz > 2000000000LL || nrows > 2000000000LL || ncols > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");
+    std::vector<int> pos((size_t)nrows + 1, 0), map((size_t)nnz);
+    for (int64_t k = 0; k < nnz; ++k) pos[(size_t)ri[(size_t)k] + 1]++;
+    for (int64_t i = 0; i < nrows; ++i) pos[(size_t)i + 1] += pos[(size_t)i];
+    for (int64_t k = 0; k < nnz; ++k) map[(size_t)pos[(size_t)ri[(size_t)k]]++] = (int)k;   // entries visited in CSC order, as csc_to_csr_pair visits them
+    return map;
+}
+
 CsrHost csc_as_transposed_csr(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz) {
     const int64_t nnz = cp[(size_t)ncols];
     if (nnz > 2000000000LL || nrows > 2000000000LL || ncols > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");

@@ -42,6 +42,9 @@ struct CsrHost { int nrows = 0, ncols = 0; std::vector<int> rp, ci; std::vector<
 // A canonical CSC matrix (nrows x ncols) as two CSR matrices: `cols` = its transpose (the CSC arrays themselves, narrowed to int32) and `rows` =
 // the matrix by rows (counting sort over the columns: column indices come out sorted inside every row).
 void csc_to_csr_pair(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz, CsrHost& rows, CsrHost& cols);
+// Where the by-rows copy of csc_to_csr_pair took its values from: rows.va[k] == nz[map[k]], map a permutation of [0, nnz).  What a value refresh on a frozen
+// pattern needs (qps_update_shared_matrices_csc); the pattern alone decides it.
+std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri);
 // The CSC arrays of a canonical matrix (nrows x ncols) read as the CSR of its transpose (ncols x nrows) -- for a symmetric P that is P itself.
 CsrHost csc_as_transposed_csr(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz);
 // [top; bottom] stacked (same column count)

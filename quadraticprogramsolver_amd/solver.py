@@ -351,6 +351,21 @@ class QuadraticProgramSharedBatch(_Handle):
         ptr = lambda a: None if a is None else _dp(a)
         _lib.check(_lib.lib().qps_update_shared_vectors(self._h, ptr(q), ptr(l), ptr(u)), self._h)
 
+    def update_matrices(self, mP=None, mA=None):
+        """Replaces the values of ``mP`` and / or ``mA`` in place (qps_update_shared_matrices; ``None`` keeps that matrix): same shapes as at creation.  Every option,
+        q, l, u, the stored z and y and all allocations stay, so ``set_warm_start("state")`` carries on across the change; the next ``solve`` factorises, also with
+        ``reuseFactor=True`` (with it, an update of ``mP`` alone skips the product A'A).  With equilibration on, the handle keeps its D and E; ``set_equilibration``
+        again computes them from the new matrices.  A refused call leaves the handle as it was."""
+        dense = lambda M: np.asfortranarray(np.asarray(M.toarray() if sp.issparse(M) else M, dtype=np.float64))
+        Pd = None if mP is None else dense(mP)
+        Ad = None if mA is None else dense(mA)
+        if Pd is not None and Pd.shape != (self.n, self.n):
+            raise ValueError(f"dimension mismatch: mP has shape {Pd.shape}, expected {(self.n, self.n)}")
+        if Ad is not None and Ad.shape != (self.m, self.n):
+            raise ValueError(f"dimension mismatch: mA has shape {Ad.shape}, expected {(self.m, self.n)}")
+        ptr = lambda a: None if a is None else _dp(a)
+        _lib.check(_lib.lib().qps_update_shared_matrices(self._h, ptr(Pd), max(self.n, 1), ptr(Ad), max(self.m, 1)), self._h)
+
     def set_rho_scale(self, vS=None):
         """Per-constraint ρ scale shared by all columns (qps_set_shared_rho_scale): row i runs with ρ_i = ρ vS[i]; ``vS`` has m finite, strictly
         positive entries (``equality_rho_scale`` builds the usual one).  ``None`` goes back to the scalar ρ.  Either way the next ``solve``
@@ -481,17 +496,33 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
         self.count = q.shape[0]
         l, u = self._rows(mL, "mL", self.m), self._rows(mU, "mU", self.m)
         _validate_dims(self.n, mP, q[0], mA, l[0], u[0])          # (every row of mQ / mL / mU has the length of the first)
-        Pc = sp.csc_matrix(mP, dtype=np.float64)
-        Ac = sp.csc_matrix(mA, dtype=np.float64)
-        Pc.sum_duplicates()
-        Ac.sum_duplicates()
-        Pcp, Pri, Pnz = Pc.indptr.astype(np.int64), Pc.indices.astype(np.int64), np.ascontiguousarray(Pc.data)
-        Acp, Ari, Anz = Ac.indptr.astype(np.int64), Ac.indices.astype(np.int64), np.ascontiguousarray(Ac.data)
+        (Pcp, Pri, Pnz), (Acp, Ari, Anz) = self._csc(mP), self._csc(mA)
         h = C.c_void_p()
         dt = {"f64": QPS_F64, "f32": QPS_F32}[dtype]
         _lib.check(getattr(_lib.lib(), self._create)(self.count, self.n, self.m, _ip(Pcp), _ip(Pri), _dp(Pnz), _ip(Acp), _ip(Ari), _dp(Anz),
                                                       _dp(q), _dp(l), _dp(u), 0, dt, device, C.byref(h)))
         self._h = h
+
+    @staticmethod
+    def _csc(M):
+        """(colptr, rowval, nzval) as the library takes them: what ``scipy.sparse.csc_matrix`` makes of ``M``, duplicates summed -- the same input gives the same
+        stored pattern at creation and at ``update_matrices`` (an explicit zero stays an entry)."""
+        Mc = sp.csc_matrix(M, dtype=np.float64)
+        Mc.sum_duplicates()
+        return Mc.indptr.astype(np.int64), Mc.indices.astype(np.int64), np.ascontiguousarray(Mc.data)
+
+    def update_matrices(self, mP=None, mA=None):
+        """Replaces the values of ``mP`` and / or ``mA`` in place (qps_update_shared_matrices_csc; ``None`` keeps that matrix): anything ``scipy.sparse.csc_matrix``
+        accepts, with the shape and the stored pattern of creation (QPS_ERR_BAD_ARGUMENT names the matrix and the first column that differs).  Ordering, symbolic
+        factor, every option, q, l, u and the stored z and y stay; the next ``solve`` runs the numeric factorisation, also with ``reuseFactor=True``.  With
+        equilibration on, the handle keeps its D and E.  A refused call leaves the handle as it was."""
+        for M, name, shape in ((mP, "mP", (self.n, self.n)), (mA, "mA", (self.m, self.n))):
+            if M is not None and tuple(getattr(M, "shape", ())) != shape:
+                raise ValueError(f"dimension mismatch: {name} has shape {getattr(M, 'shape', None)}, expected {shape}")
+        Pcp, Pri, Pnz = (None, None, None) if mP is None else self._csc(mP)
+        Acp, Ari, Anz = (None, None, None) if mA is None else self._csc(mA)
+        ip, dp = (lambda a: None if a is None else _ip(a)), (lambda a: None if a is None else _dp(a))
+        _lib.check(_lib.lib().qps_update_shared_matrices_csc(self._h, ip(Pcp), ip(Pri), dp(Pnz), ip(Acp), ip(Ari), dp(Anz), 0), self._h)
 
     def solve(self, mX=None, *, linsys="auto", **kw):
         """As ``QuadraticProgramSharedBatch.solve``; ``linsys`` ("auto" or "ldl": the sparse L D L' either way) goes to the library as it is."""
