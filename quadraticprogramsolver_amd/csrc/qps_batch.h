@@ -1,5 +1,5 @@
-// qps_batch.h -- what the batch handles share between qps_capi.hip (handle plumbing), qps_dense_batch.hip (BatchedDenseSolver) and qps_shared_batch.hip (the
-// shared-matrix family): the base of every fused batch solver, the one interface the qps_*_shared_* entry points talk to, the factories of all three, and the
+// qps_batch.h -- what the batch handles share between qps_capi.hip (handle plumbing), qps_dense_batch.hip (BatchedDenseSolver) and the shared-matrix family
+// (qps_shared_family.h: the driver; qps_shared_dense.hip, qps_shared_csr.hip: its three paths): the base of every fused batch solver, the one interface the qps_*_shared_* entry points talk to, the factories of all three, and the
 // panelled matrix upload.
 #pragma once
 #include "ldl_symbolic.h"

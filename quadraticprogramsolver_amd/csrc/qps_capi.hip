@@ -1,5 +1,5 @@
 // qps_capi.hip -- the C ABI of include/qps.h and nothing else: the handle table, argument validation and problem import of every entry point.  The solvers live
-// behind factories: make_dense (qps_dense.hip), make_dense_batch (qps_dense_batch.hip), the shared-matrix batches (qps_shared_batch.hip), make_sparse_solver
+// behind factories: make_dense (qps_dense.hip), make_dense_batch (qps_dense_batch.hip), the shared-matrix batches (qps_shared_dense.hip, qps_shared_csr.hip), make_sparse_solver
 // (qps_sparse.hip) and ProxQP, dense and sparse (qps_proxqp.hip); the per-device resource pools are in qps_runtime.hip.
 //
 // An entry point tests its arguments in a fixed order and words every refusal itself; tests/test_capi_errors_cpu.py pins status, text and order.

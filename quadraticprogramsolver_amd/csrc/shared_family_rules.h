@@ -1,4 +1,4 @@
-// shared_family_rules.h -- the two host-side rules of the shared-matrix batches (qps_shared_batch.hip): the equilibration step and the family-wide rho proposal.
+// shared_family_rules.h -- the two host-side rules of the shared-matrix batches (qps_shared_family.h): the equilibration step and the family-wide rho proposal.
 // Plain host arithmetic, no HIP: the CPU suite calls them through tests/capi/layout_shim.cpp and holds them to the numpy restatements of
 // tests/equilibration_cases.py and tests/family_rho_cases.py.
 #pragma once

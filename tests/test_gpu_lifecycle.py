@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from cg_shared_cases import COUNT as CG_COUNT, banded_family
+from matrix_update_cases import step_matrices
 from shared_batch_cases import shared_family
 from sparse_shared_cases import lasso_path
 
@@ -59,6 +61,8 @@ def _cycles(q):
     # 20 columns are 32 panel columns: one state panel is 32 x 2048 (2448 sparse) doubles = 512 (612) KiB, so one panel leaked per cycle shows as >= 6 MiB
     dense_family = shared_family(1024, 2048, 20)
     sparse_family = lasso_path(24, 20)                          # n = m = 2448
+    sparse_family_2 = step_matrices(*sparse_family[:2], 1)
+    cg_family = banded_family(CG_COUNT)                         # the smallest family of tests/cg_shared_cases.py: n = 70, m = 139
 
     def run_dense(problem, dtype, **kw):
         P, qq, A, l, u = problem
@@ -88,15 +92,34 @@ def _cycles(q):
             z, y = prob.dual()
             prob.polish(x, y)
 
-    def run_shared(cls, family):
+    def run_shared(cls, family, updated=None):
+        """updated: the second matrices of the family -- the infeasibility option on, and qps_update_shared_matrices* between the two solves (the staging of the
+        new values, the position map, the per-entry exponents and the certificate panels come and go with the handle)."""
         P, A, Q, L, U = family
         with cls(P, A, Q, L, U) as fam:
             fam.set_rho_scale(q.equality_rho_scale(L, U))
             fam.set_equilibration(10)
             fam.set_adaptive_rho(True)
             fam.set_warm_start("state")
-            for _ in range(2):
+            if updated:
+                fam.set_infeasibility(1e-4, 1e-4)
+            for k in range(2):
                 fam.solve(numIterations=60, ϵAbs=0.0, ϵRel=0.0, ρ=0.1, numItrConv=25)
+                if updated and k == 0:
+                    fam.update_matrices(*updated)
+            fam.dual()
+
+    def run_shared_cg():
+        P, A, Q, L, U = cg_family
+        with q.QuadraticProgramCgSharedBatch(P, A, Q, L, U) as fam:
+            fam.set_rho_scale(q.equality_rho_scale(L, U))
+            fam.set_adaptive_rho(True)
+            fam.set_warm_start("state")
+            fam.set_infeasibility(1e-4, 1e-4)
+            X, _, _ = fam.solve(numIterations=60, ϵAbs=0.0, ϵRel=0.0, ρ=1.0, numItrConv=25)
+            fam.update_matrices(*step_matrices(P, A, 1))
+            X, _, _ = fam.solve(X, numIterations=60, ϵAbs=0.0, ϵRel=0.0, ρ=1.0, numItrConv=25)
+            fam.polish(X)
             fam.dual()
 
     return {
@@ -113,6 +136,8 @@ def _cycles(q):
         "polish": run_polish,
         "shared dense f64, all options": lambda: run_shared(q.QuadraticProgramSharedBatch, dense_family),
         "shared sparse f64, all options": lambda: run_shared(q.QuadraticProgramSparseSharedBatch, sparse_family),
+        "shared sparse f64, all options, matrices updated": lambda: run_shared(q.QuadraticProgramSparseSharedBatch, sparse_family, sparse_family_2),
+        "shared cg f64, all options, matrices updated": run_shared_cg,
     }
 
 

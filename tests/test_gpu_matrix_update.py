@@ -140,10 +140,10 @@ def test_options_and_state_are_carried(gpu, key):
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. equilibration on: the exponents are kept, exactly
 # ---------------------------------------------------------------------------------------------------------------------
-def scaled_twin_data(key, D, E):
-    """(D P2 D, E A2 D, D q, E l, E u): exact, D and E are powers of two."""
+def scaled_twin_data(key, D, E, k=1):
+    """(D P_k D, E A_k D, D q, E l, E u): exact, D and E are powers of two."""
     _, _, Q, L, U = mc.data(key)
-    P2, A2 = mc.matrices(key, 1)
+    P2, A2 = mc.matrices(key, k)
     if sp.issparse(P2):
         Pc, Ac = mc.canonical(P2), mc.canonical(A2)
         n = Pc.shape[0]
@@ -182,6 +182,73 @@ def test_kept_exponents_are_exact(gpu, key):
         want = run(f, **kw)
     assert np.array_equal(Dn, Df) and np.array_equal(En, Ef)
     assert same(again, want)
+
+
+OTHER_PASSES = 3                                                           # a second scaling: on these matrices its exponents are not those of mc.PASSES
+
+
+def test_a_change_of_scaling_between_two_updates(gpu):
+    """Sparse L D L' handle: scaling of mc.PASSES passes, update to step 1, scaling of OTHER_PASSES passes, update to step 2, scaling off, update to step 3; a
+    solve of mc.FIXED_ITERATIONS iterations at every stop.  The per-entry exponents of the update are built under the first scaling, dropped and rebuilt under
+    the second, and gone with the third.
+
+    An update keeps the exponents of the matrices it found, and those are not the exponents a fresh handle computes from the new matrices (on these families
+    they differ at every step and every pass count).  So the fresh handle "on those matrices with the same options" is: right after an update under a scaling,
+    the unscaled twin on (D P_k D, E A_k D) of test 5 -- X, Y, Z exact through D and E, flags and iteration counts equal, D and E unchanged by the update; after
+    every change of scaling and after the unscaled update, a fresh handle with that pass count -- ``same()``: X, Z, Y and every qps_info field but the times --
+    and its exponent vectors."""
+    key = mc.SCRAMBLED_SPARSE
+    kw = dict(numIterations=mc.FIXED_ITERATIONS, ϵAbs=0.0, ϵRel=0.0, ρ=mc.rho_of(key))
+
+    def fresh_with(k, passes):
+        with make(gpu, key, k, k) as f:
+            f.set_equilibration(passes)
+            return run(f, **kw), f.equilibration()
+
+    def update_under_kept_exponents(h, k):
+        D, E = h.equilibration()
+        assert (D != 1).any() and (E != 1).any()
+        h.update_matrices(*mc.matrices(key, k))
+        assert all(np.array_equal(a, b) for a, b in zip(h.equilibration(), (D, E)))
+        r = run(h, **kw)
+        with gpu.QuadraticProgramSparseSharedBatch(*scaled_twin_data(key, D, E, k)) as twin:
+            t = run(twin, **kw)
+        assert np.array_equal(r["X"], D * t["X"]) and np.array_equal(r["Y"], E * t["Y"]) and np.array_equal(r["Z"], t["Z"] / E), k
+        assert r["flags"] == t["flags"] and [i["iterations"] for i in r["infos"]] == [i["iterations"] for i in t["infos"]]
+
+    def equals_fresh(h, k, passes):
+        want, (Df, Ef) = fresh_with(k, passes)
+        D, E = h.equilibration()
+        assert np.array_equal(D, Df) and np.array_equal(E, Ef), (k, passes)
+        assert same(run(h, **kw), want), (k, passes)
+        return D, E
+
+    with make(gpu, key) as h:
+        h.set_equilibration(mc.PASSES)
+        update_under_kept_exponents(h, 1)
+        D1, E1 = h.equilibration()
+        h.set_equilibration(OTHER_PASSES)
+        D2, E2 = equals_fresh(h, 1, OTHER_PASSES)
+        assert not (np.array_equal(D1, D2) and np.array_equal(E1, E2))    # the scaling did change between the two updates
+        update_under_kept_exponents(h, 2)
+        h.set_equilibration(0)
+        equals_fresh(h, 2, 0)
+        h.update_matrices(*mc.matrices(key, 3))
+        equals_fresh(h, 3, 0)
+
+
+def test_three_updates_in_a_row_on_a_cg_handle(gpu):
+    """The unscaled part of the sequence above on the CG handle, which refuses the equilibration: after each of three updates a solve of mc.FIXED_ITERATIONS
+    iterations equals a fresh handle's on those matrices."""
+    key = mc.CG_BANDED
+    kw = dict(numIterations=mc.FIXED_ITERATIONS, ϵAbs=0.0, ϵRel=0.0, ρ=mc.rho_of(key))
+    with make(gpu, key) as h:
+        for k in (1, 2, 3):
+            h.update_matrices(*mc.matrices(key, k))
+            got = run(h, **kw)
+            with make(gpu, key, k, k) as f:
+                assert same(got, run(f, **kw)), k
+
 
 
 # ---------------------------------------------------------------------------------------------------------------------

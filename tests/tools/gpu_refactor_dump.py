@@ -2,13 +2,17 @@
 plugin calls of a dense handle.  One dump per build, each in a fresh process; `compare` then demands that every array and every qps_info field except the
 times is bitwise equal.  Not a test.
 
-    python tests/tools/gpu_refactor_dump.py dump OUT.npz [--lib PATH/libqps_hip.so] [--group dense|sparse]
+    python tests/tools/gpu_refactor_dump.py dump OUT.npz [--lib PATH/libqps_hip.so] [--group dense|sparse|shared]
     python tests/tools/gpu_refactor_dump.py compare A.npz B.npz
-    python tests/tools/gpu_refactor_dump.py cycle [--lib PATH] [--cycles N] [--group dense|sparse]   # create + solve + destroy at 64 x 128 (sparse: of a small
-                                                                                # CSC and a small sparse ProxQP handle): median microseconds per cycle
+    python tests/tools/gpu_refactor_dump.py cycle [--lib PATH] [--cycles N] [--group dense|sparse|shared]   # create + solve + destroy at 64 x 128 (sparse: of a
+                                                                                # small CSC and a small sparse ProxQP handle; shared: of one small handle per
+                                                                                # kind of the shared-matrix batches): median microseconds per cycle
 
 The routes are those named in tests/loop_param_cases.py.  `--group sparse` covers the CSC handle instead -- the CG plugin on every product form, the explicit
-reduced matrix, the direct KKT plugin, AUTO, polishing, the plugin calls, the five operators -- and the sparse ProxQP form.  QPS_GRAPH is read once per process: a
+reduced matrix, the direct KKT plugin, AUTO, polishing, the plugin calls, the five operators -- and the sparse ProxQP form.  `--group shared` covers the three
+handle kinds of the shared-matrix batches (dense Cholesky, sparse KKT L D L', matrix-free CG) on two small families each: fixed 50 iterations, to eps = 1e-6, rho
+scale, family rho, equilibration, both warm start modes, certificates, polishing at the end of a solve and as a call, update() + reuseFactor, the three forms of
+update_matrices, and every option together.  QPS_GRAPH is read once per process: a
 dump started with QPS_GRAPH=0 runs the direct plugin's routes alone, eagerly, under their own tags."""
 import contextlib
 import os
@@ -243,6 +247,120 @@ def dump_sparse(q, path):
     print("wrote", path, len(out), "arrays")
 
 
+def dump_shared(q, path):
+    """The three handle kinds of the shared-matrix batches on the small families of the suite, every option of the family on its own and all together."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cg_shared_cases as cc
+    from matrix_update_cases import step_matrices
+    from shared_batch_cases import shared_family
+    from sparse_shared_cases import lasso_path, random_family
+    out = {}
+    families = [("dense_96x160", q.QuadraticProgramSharedBatch, shared_family(96, 160, 6), RHO),
+                ("dense_1100x2300", q.QuadraticProgramSharedBatch, shared_family(1100, 2300, 20), RHO),          # two panels
+                ("sparse_lasso", q.QuadraticProgramSparseSharedBatch, lasso_path(10, 6), RHO),
+                ("sparse_random", q.QuadraticProgramSparseSharedBatch, random_family(20), RHO),
+                ("cg_random", q.QuadraticProgramCgSharedBatch, cc.family("random"), cc.RHO["random"]),
+                ("cg_banded", q.QuadraticProgramCgSharedBatch, cc.family("banded"), cc.RHO["banded"])]
+
+    def put(tag, h, X, infos, reps=None, cert=False, eq=False):
+        Z, Y = h.dual()
+        out[tag + "/X"], out[tag + "/Z"], out[tag + "/Y"] = np.array(X), np.array(Z), np.array(Y)
+        out[tag + "/info"] = np.stack([info_array(i)[1] for i in infos])
+        if reps is not None:
+            out[tag + "/polish"] = np.array([[float(r[k]) for k in sorted(r) if k != "seconds"] for r in reps])
+        if cert:
+            out[tag + "/certDY"], out[tag + "/certDX"] = (np.array(a) for a in h.certificate())
+        if eq:
+            out[tag + "/eqD"], out[tag + "/eqE"] = (np.array(a) for a in h.equilibration())
+        print(f"{tag:44s} iterations={[i['iterations'] for i in infos][:6]} convFlag={[i['convFlag'] for i in infos][:6]} numRefactor={[i['numRefactor'] for i in infos][:3]}",
+              flush=True)
+
+    for name, cls, (P, A, Q, L, U), rho in families:
+        cg = cls is q.QuadraticProgramCgSharedBatch
+        fixed = dict(numIterations=50, numItrConv=25, ϵAbs=0.0, ϵRel=0.0, ρ=rho)
+        to_eps = dict(numIterations=2000, numItrConv=5, ϵAbs=1e-6, ϵRel=1e-6, ρ=rho)               # a check every 5 iterations: the columns stop at different checks
+        vS = q.equality_rho_scale(L, U, 1e2)
+        vS[0] = 10.0                                                                                # not all ones on any family
+        P2, A2 = step_matrices(P, A, 1)
+
+        def everything(h):
+            h.set_rho_scale(vS)
+            h.set_adaptive_rho(True)
+            if not cg:
+                h.set_equilibration(10)
+            h.set_warm_start("state")
+            h.set_infeasibility(1e-4, 1e-4)
+            h.set_polish(True)
+
+        def route(tag, dtype, prepare=None, second=None, kw=fixed, **flags):
+            """One fresh handle: prepare(h), a solve from X = 0; then second(h, X) -> (X0, kw) and a second solve, dumped under .2"""
+            t = f"{name}.{tag}.{dtype}"
+            with cls(P, A, Q, L, U, dtype=dtype) as h:
+                try:
+                    if prepare:
+                        prepare(h)
+                    X, _, infos = h.solve(**kw)
+                    put(t, h, X, infos, **flags)
+                    if second:
+                        X0, kw2 = second(h, X)
+                        X, _, infos = h.solve(X0, **kw2)
+                        put(t + ".2", h, X, infos, **flags)
+                except q.QpsError as e:                                                             # a refusal is part of the record: its text must not move
+                    out[t + "/refused"] = np.frombuffer(str(e).encode(), dtype=np.uint8)
+                    print(f"{t:44s} refused: {e}", flush=True)
+
+        def all_together(h, X):
+            h.update(Q[::-1].copy(), L[::-1].copy(), U[::-1].copy())
+            h.update_matrices(P2, A2)
+            return X, dict(to_eps, fctrΡ=1.5, reuseFactor=True)
+
+        for dtype in ("f64", "f32"):
+            route("fixed50", dtype)
+            route("all_options", dtype, everything, all_together, kw=dict(to_eps, fctrΡ=1.5), cert=True, eq=not cg)
+        route("to_eps", "f64", kw=to_eps)
+        route("rho_scale", "f64", lambda h: h.set_rho_scale(q.equality_rho_scale(L, U)), kw=to_eps)
+        route("family_rho", "f64", lambda h: h.set_adaptive_rho(True), kw=dict(to_eps, fctrΡ=1.5))
+        if not cg:
+            route("equilibration", "f64", lambda h: h.set_equilibration(10), kw=to_eps, eq=True)
+        route("warm_state", "f64", lambda h: h.set_warm_start("state"), lambda h, X: (X, to_eps))
+        route("warm_ax", "f64", lambda h: h.set_warm_start("ax"), lambda h, X: (X, to_eps))
+        route("infeasibility", "f64", lambda h: h.set_infeasibility(1e-4, 1e-4), kw=to_eps, cert=True)
+        route("update_reuse", "f64", None, lambda h, X: (h.update(Q[::-1].copy(), L[::-1].copy(), U[::-1].copy()), (None, dict(fixed, reuseFactor=True)))[1])
+        for tag, mats in (("update_P", dict(mP=P2)), ("update_A", dict(mA=A2)), ("update_PA", dict(mP=P2, mA=A2))):
+            route(tag, "f64", None, lambda h, X, mats=mats: (h.update_matrices(**mats), (None, fixed))[1])
+        with cls(P, A, Q, L, U) as h:                                                               # polishing: at the end of a solve, and from the caller's x and y
+            h.set_polish(True)
+            X, _, infos = h.solve(**to_eps)
+            put(f"{name}.polish_on.f64", h, X, infos)
+            h.set_polish(False)
+            X, _, infos = h.solve(**to_eps)
+            Z, Y = h.dual()
+            Xp = np.array(X)
+            reps = h.polish(Xp, np.array(Y))
+            put(f"{name}.polish_call.f64", h, Xp, infos, reps=reps)
+    np.savez(path, **out)
+    print("wrote", path, len(out), "arrays")
+
+
+def cycle_shared(q, cycles):
+    """create + solve + destroy of one small handle per kind of the shared-matrix batches: median microseconds per cycle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cg_shared_cases as cc
+    from shared_batch_cases import shared_family
+    from sparse_shared_cases import random_family
+    for name, cls, fam, rho in (("dense shared 96x160x6", q.QuadraticProgramSharedBatch, shared_family(96, 160, 6), RHO),
+                                ("sparse shared random_family(20)", q.QuadraticProgramSparseSharedBatch, random_family(20), RHO),
+                                ("cg shared banded_family(20)", q.QuadraticProgramCgSharedBatch, cc.family("banded"), cc.RHO["banded"])):
+        ts = []
+        for k in range(cycles + 20):
+            t0 = time.perf_counter()
+            with cls(*fam) as h:
+                h.solve(numIterations=50, numItrConv=25, ϵAbs=0.0, ϵRel=0.0, ρ=rho)
+            ts.append(time.perf_counter() - t0)
+        ts = np.array(ts[20:]) * 1e6
+        print(f"create+solve+destroy {name}: median_us={np.median(ts):.1f} min_us={ts.min():.1f} p90_us={np.percentile(ts, 90):.1f} cycles={cycles}", flush=True)
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     bad = sorted(set(A.files) ^ set(B.files))
@@ -319,11 +437,12 @@ def cycle_sparse(q, cycles):
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
+    group = argv[argv.index("--group") + 1] if "--group" in argv else "dense"
     if argv and argv[0] == "dump":
-        (dump_sparse if "sparse" in argv[2:] else dump)(library(argv), argv[1])
+        {"dense": dump, "sparse": dump_sparse, "shared": dump_shared}[group](library(argv), argv[1])
     elif argv and argv[0] == "compare":
         sys.exit(compare(argv[1], argv[2]))
     elif argv and argv[0] == "cycle":
-        (cycle_sparse if "sparse" in argv[1:] else cycle)(library(argv), int(argv[argv.index("--cycles") + 1]) if "--cycles" in argv else 300)
+        {"dense": cycle, "sparse": cycle_sparse, "shared": cycle_shared}[group](library(argv), int(argv[argv.index("--cycles") + 1]) if "--cycles" in argv else 300)
     else:
         raise SystemExit(__doc__)
