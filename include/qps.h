@@ -267,6 +267,22 @@ int32_t qps_set_shared_rho_scale(qps_handle h, const double *scale /* [m]; NULL 
  * not a shared-matrix batch. */
 int32_t qps_set_shared_adaptive_rho(qps_handle h, int32_t mode /* 0 fixed rho, 1 family-wide rule */);
 
+/* Per-column adaptive rho of a matrix-free CG shared-matrix batch handle (qps_create_csc_shared_batch_cg), opt-in: the reference's own per-problem rule
+ * (SolveQuadraticProgram.jl:43, :47, :92-96) for every column.  Nothing is factorised on that handle and rho enters three kernels as a multiplier, so every
+ * column can carry a rho of its own: rho_b = qps_params.rho at the start of every solve (warm start modes do not carry rho across solves); at a check
+ * rhorho_b = clamp(rho_b sqrt(normResPrim_b maxNormDual_b / (normResDual_b maxNormPrim_b)), 1e-3, 1e6) from the column's own four norms; at the top of the
+ * next iteration rhorho_b fctrRho < rho_b || rhorho_b > fctrRho rho_b makes rho_b = rhorho_b.  A NaN proposal never switches, a column that has stopped keeps its
+ * rho, and a column's CG continues from its x~ across a switch.  Column b then equals a stand-alone CSC handle with QPS_LINSYS_CG, matrix-free, adptRho = 1.
+ * With a per-row rho scale row i of column b runs on rho_b s_i.  qps_info per column: numRefactor = its own switches, rhoFinal = its rho, rhoProposed = its
+ * last proposal.  The batch runs until its slowest column: the gain is per column.  The option is a property of the handle, survives
+ * qps_update_shared_matrices_csc and excludes the family rule: turning one on while the other is on is QPS_ERR_UNSUPPORTED (turn the other off first; the
+ * handle stays as it was), turning either off is always accepted.  While it is on, qps_solve_batch wants fctrRho > 0 (QPS_ERR_BAD_ARGUMENT); adptRho = 1 in
+ * qps_params stays refused.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, `on` outside {0, 1} (before a device is needed).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): a handle that is
+ * not a shared-matrix batch; on = 1 on a dense or a sparse L D L' shared-matrix batch, where one factor serves every column (they have
+ * qps_set_shared_adaptive_rho). */
+int32_t qps_set_shared_column_rho(qps_handle h, int32_t on /* 0 = off (default); 1 = every column moves its own rho */);
+
 /* Ruiz equilibration of a shared-matrix batch handle (dense or sparse; section 5.1 of the OSQP paper, item 2 of the reference's to-do list), opt-in: passes = 0
  * (the default) leaves the handle exactly as it is, passes = 1..50 runs that many passes.  The scaling D = diag(2^kd) of the variables and E = diag(2^ke) of the
  * constraints depends on P and A only, so it is computed once for the family and serves every column and every re-solve after qps_update_shared_vectors.  D and E

@@ -458,6 +458,14 @@ function SharedBatchSetAdaptiveRho!(sb::SharedBatchHip, on::Bool = true)
     return nothing
 end
 
+# Per-column adaptive ρ (qps_set_shared_column_rho), matrix-free CG shared-matrix batches only: every column moves its own ρ by the reference's rule from its own
+# norms (adptΡ = true per column); excludes SharedBatchSetAdaptiveRho!.  false goes back to the fixed ρ.  The setting stays with the handle.
+function SharedBatchSetColumnRho!(sb::SharedBatchHip, on::Bool = true)
+    h = sb.h
+    _check(ccall((:qps_set_shared_column_rho, LIBQPS), Int32, (Ptr{Cvoid}, Int32), h, on ? 1 : 0), h)
+    return nothing
+end
+
 # Ruiz equilibration with exact powers of two (qps_set_shared_equilibration; OSQP §5.1), opt-in: passes = 1..50 passes of the rule, computed once for the family
 # from mP and mA; 0 or nothing switches it off and restores the matrices bit for bit.  Warm starts, results, duals and the convergence check stay in the caller's
 # units.  Setting, changing or clearing makes the next SharedBatchSolve! factorise, also with reuseFactor = true.

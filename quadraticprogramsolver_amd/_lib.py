@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = [
     "qps_create_dense_shared_batch", "qps_update_shared_vectors", "qps_create_csc_shared_batch", "qps_set_shared_rho_scale",
     "qps_set_shared_adaptive_rho", "qps_set_shared_equilibration", "qps_get_shared_equilibration", "qps_set_shared_warm_start", "qps_set_shared_dual",
     "qps_set_shared_infeasibility", "qps_get_shared_certificate", "qps_polish_shared", "qps_set_shared_polish",
-    "qps_create_csc_shared_batch_cg", "qps_update_shared_matrices", "qps_update_shared_matrices_csc",
+    "qps_create_csc_shared_batch_cg", "qps_update_shared_matrices", "qps_update_shared_matrices_csc", "qps_set_shared_column_rho",
 ]
 
 QPS_OK = 0
@@ -148,6 +148,7 @@ def lib() -> C.CDLL:
     L.qps_update_shared_matrices_csc.argtypes = [hp, ip, ip, dp, ip, ip, dp, i32]
     L.qps_set_shared_rho_scale.argtypes = [hp, dp]
     L.qps_set_shared_adaptive_rho.argtypes = [hp, i32]
+    L.qps_set_shared_column_rho.argtypes = [hp, i32]
     L.qps_set_shared_equilibration.argtypes = [hp, i32]
     L.qps_get_shared_equilibration.argtypes = [hp, dp, dp]
     L.qps_set_shared_warm_start.argtypes = [hp, i32]

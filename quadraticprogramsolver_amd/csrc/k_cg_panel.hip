@@ -70,19 +70,25 @@ __global__ __launch_bounds__(PS_THREADS) void k_cgp_rhs(int n, int m, const int*
     if (valid && strip == 0) { const int64_t i = ((int64_t)blockIdx.y * n + r) * 16 + col; t[i] = sigma * x[i] - q[i] + s; }
 }
 
-// first launch of the operator: v = rho_i (A u).  st != NULL: a panel whose columns are all done is skipped
-template <typename T, int SPR>
+// rho of (row r, column c of the batch) under qps_set_shared_column_rho: rho_b, times s_i where a row scale is set (rho_row then holds s_i: two roundings)
+template <typename T> __device__ __forceinline__ T cgp_col_rho(T rc, const T* __restrict__ rho_row, int r) { return rho_row ? rc * rho_row[r] : rc; }
+
+// first launch of the operator: v = rho_i (A u).  st != NULL: a panel whose columns are all done is skipped.  COL: rho_b of the thread's column from rho_col --
+// the 16 values of a panel are one line, loaded once per thread before the strips
+template <typename T, int SPR, bool COL>
 __global__ __launch_bounds__(PS_THREADS) void k_cgp_av(int m, int n, const int* __restrict__ rp, const int* __restrict__ ci, const T* __restrict__ va,
-                                                        const T* __restrict__ u, const T* __restrict__ rho_row, T rho, const CgPanelState* __restrict__ st,
-                                                        T* __restrict__ v) {
+                                                        const T* __restrict__ u, const T* __restrict__ rho_row, T rho, const T* __restrict__ rho_col,
+                                                        const CgPanelState* __restrict__ st, T* __restrict__ v) {
     const int r = blockIdx.x * (PS_THREADS / (16 * SPR)) + threadIdx.x / (16 * SPR), strip = (threadIdx.x >> 4) % SPR, col = threadIdx.x & 15;
     if (st && __syncthreads_and(st[blockIdx.y * 16 + col].done)) return;
     const bool valid = r < m;
     const T* up = u + (int64_t)blockIdx.y * n * 16 + col;
+    T rc = rho;
+    if (COL) rc = rho_col[blockIdx.y * 16 + col];
     T s = T(0);
     if (valid) s = strip_dot<T, SPR>(rp[r], rp[r + 1], strip, ci, va, [&](int i) { return up[(int64_t)i * 16]; });
     s = strips_sum<T, SPR>(s);
-    if (valid && strip == 0) v[((int64_t)blockIdx.y * m + r) * 16 + col] = (rho_row ? rho_row[r] : rho) * s;
+    if (valid && strip == 0) v[((int64_t)blockIdx.y * m + r) * 16 + col] = (COL ? cgp_col_rho(rc, rho_row, r) : (rho_row ? rho_row[r] : rho)) * s;
 }
 
 // second launch of the operator: row r of P over u, then row r of A' over v, c_r = that + sigma u_r (LinearSystemSolvers.jl:152-157).
@@ -203,21 +209,26 @@ __global__ __launch_bounds__(256) void k_cgp_finish(const double* __restrict__ p
     }
 }
 
-// z~ = A x~ (LinearSystemSolvers.jl:181) with the row update of SolveQuadraticProgram.jl:59-61 as its epilogue, on the active columns; rho_i where a scale is set
-template <typename T, int SPR>
+// z~ = A x~ (LinearSystemSolvers.jl:181) with the row update of SolveQuadraticProgram.jl:59-61 as its epilogue, on the active columns; rho_i where a scale is set.
+// COL: rho_b and 1 / rho_b of the thread's column from rho_col / rho1_col, as in k_cgp_av
+template <typename T, int SPR, bool COL>
 __global__ __launch_bounds__(PS_THREADS) void k_cgp_post_rows(int m, int n, const int* __restrict__ rp, const int* __restrict__ ci, const T* __restrict__ va,
                                                               const T* __restrict__ xx, T* __restrict__ z, T* __restrict__ zp, T* __restrict__ y,
                                                               const T* __restrict__ lo, const T* __restrict__ hi, const int* __restrict__ active, T alpha, T rho,
-                                                              const T* __restrict__ rho_row, const T* __restrict__ rho1_row) {
+                                                              const T* __restrict__ rho_row, const T* __restrict__ rho1_row, const T* __restrict__ rho_col,
+                                                              const T* __restrict__ rho1_col) {
     const int r = blockIdx.x * (PS_THREADS / (16 * SPR)) + threadIdx.x / (16 * SPR), strip = (threadIdx.x >> 4) % SPR, col = threadIdx.x & 15;
     const bool valid = r < m;
     const T* xp = xx + (int64_t)blockIdx.y * n * 16 + col;
+    T rc = rho, rc1 = T(0);
+    if (COL) { rc = rho_col[blockIdx.y * 16 + col]; rc1 = rho1_col[blockIdx.y * 16 + col]; }
     T s = T(0);
     if (valid) s = strip_dot<T, SPR>(rp[r], rp[r + 1], strip, ci, va, [&](int i) { return xp[(int64_t)i * 16]; });
     s = strips_sum<T, SPR>(s);
     if (valid && strip == 0 && active[blockIdx.y * 16 + col]) {
         const int64_t i = ((int64_t)blockIdx.y * m + r) * 16 + col;
-        const T rr = rho_row ? rho_row[r] : rho, rr1 = rho_row ? rho1_row[r] : T(1) / rho, alpha1 = T(1) - alpha;
+        const T rr = COL ? cgp_col_rho(rc, rho_row, r) : (rho_row ? rho_row[r] : rho);
+        const T rr1 = COL ? cgp_col_rho(rc1, rho1_row, r) : (rho_row ? rho1_row[r] : T(1) / rho), alpha1 = T(1) - alpha;
         const T zo = z[i], yo = y[i];
         zp[i] = zo;                                                           // :59
         const T t = alpha * s + alpha1 * zo + rr1 * yo;                       // :60
@@ -239,6 +250,19 @@ __global__ __launch_bounds__(256) void k_cgp_post_x(int64_t per_panel, int64_t t
     x[i] = alpha * xx[i] + (T(1) - alpha) * xo;
 }
 
+// w = rho_b z - y on the active columns under qps_set_shared_column_rho (LinearSystemSolvers.jl:176): the expression of panel_w with the column's own rho, one
+// thread per (row, column); a stopped column keeps its w
+template <typename T>
+__global__ __launch_bounds__(256) void k_cgp_w(int64_t per_panel, int64_t total, const T* __restrict__ z, const T* __restrict__ y, const int* __restrict__ active,
+                                               const T* __restrict__ rho_row, const T* __restrict__ rho_col, T* __restrict__ w) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i / per_panel) * 16 + (int)(i & 15);
+    if (!active[c]) return;
+    const T rr = cgp_col_rho(rho_col[c], rho_row, (int)((i % per_panel) >> 4));
+    w[i] = rr * z[i] - y[i];
+}
+
 template <int SPR> constexpr int rpb_of() { return PS_THREADS / (16 * SPR); }
 
 // F(std::integral_constant<int, SPR>) for the strip count spr
@@ -252,8 +276,11 @@ template <typename T, int INIT>
 void cgp_operator(hipStream_t st, const CgPanelArgs<T>& a, const T* u, const CgPanelState* state) {
     with_spr(a.A.spr, [&](auto S) {
         constexpr int SPR = decltype(S)::value;
-        hipLaunchKernelGGL((k_cgp_av<T, SPR>), dim3((unsigned)cgp_groups(a.m, rpb_of<SPR>()), (unsigned)a.npanel), dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp, a.A.ci,
-                           a.A.va, u, a.rho_row, a.rho, INIT ? nullptr : state, a.v);
+        const dim3 grid((unsigned)cgp_groups(a.m, rpb_of<SPR>()), (unsigned)a.npanel);
+        if (a.rho_col) hipLaunchKernelGGL((k_cgp_av<T, SPR, true>), grid, dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp, a.A.ci, a.A.va, u, a.rho_row, a.rho, a.rho_col,
+                                          INIT ? nullptr : state, a.v);
+        else hipLaunchKernelGGL((k_cgp_av<T, SPR, false>), grid, dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp, a.A.ci, a.A.va, u, a.rho_row, a.rho, a.rho_col,
+                                INIT ? nullptr : state, a.v);
     });
     with_spr(a.spr_op, [&](auto S) {
         constexpr int SPR = decltype(S)::value;
@@ -303,14 +330,24 @@ template <typename T> void cg_panel_post(hipStream_t st, const CgPanelArgs<T>& a
     if (a.n <= 0 || a.m <= 0 || a.npanel <= 0) return;
     with_spr(a.A.spr, [&](auto S) {
         constexpr int SPR = decltype(S)::value;
-        hipLaunchKernelGGL((k_cgp_post_rows<T, SPR>), dim3((unsigned)cgp_groups(a.m, rpb_of<SPR>()), (unsigned)a.npanel), dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp,
-                           a.A.ci, a.A.va, (const T*)a.xx, a.z, a.zp, a.y, a.lo, a.hi, a.active, a.alpha, a.rho, a.rho_row, a.rho1_row);
+        const dim3 grid((unsigned)cgp_groups(a.m, rpb_of<SPR>()), (unsigned)a.npanel);
+        if (a.rho_col) hipLaunchKernelGGL((k_cgp_post_rows<T, SPR, true>), grid, dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp, a.A.ci, a.A.va, (const T*)a.xx, a.z, a.zp, a.y,
+                                          a.lo, a.hi, a.active, a.alpha, a.rho, a.rho_row, a.rho1_row, a.rho_col, a.rho1_col);
+        else hipLaunchKernelGGL((k_cgp_post_rows<T, SPR, false>), grid, dim3(PS_THREADS), 0, st, a.m, a.n, a.A.rp, a.A.ci, a.A.va, (const T*)a.xx, a.z, a.zp, a.y,
+                                a.lo, a.hi, a.active, a.alpha, a.rho, a.rho_row, a.rho1_row, a.rho_col, a.rho1_col);
     });
     const int64_t per = (int64_t)a.n * 16, total = per * a.npanel;
     hipLaunchKernelGGL((k_cgp_post_x<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, per, total, (const T*)a.xx, a.x, a.xp, a.active, a.alpha);
 }
 
+template <typename T> void cg_panel_w(hipStream_t st, const CgPanelArgs<T>& a, T* w) {
+    if (a.m <= 0 || a.npanel <= 0) return;
+    const int64_t per = (int64_t)a.m * 16, total = per * a.npanel;
+    hipLaunchKernelGGL((k_cgp_w<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, per, total, (const T*)a.z, (const T*)a.y, a.active, a.rho_row, a.rho_col, w);
+}
+
 #define INST(T)                                                                                  \
+    template void cg_panel_w<T>(hipStream_t, const CgPanelArgs<T>&, T*);                         \
     template void cg_panel_begin<T>(hipStream_t, const CgPanelArgs<T>&);                         \
     template void cg_panel_iteration<T>(hipStream_t, const CgPanelArgs<T>&, int, bool);          \
     template void cg_panel_finish<T>(hipStream_t, const CgPanelArgs<T>&, int);                   \

@@ -14,11 +14,13 @@ struct CanonicalCsc { bool given = false; std::vector<int64_t> cp, ri; std::vect
 // What only the shared-matrix batches take (qps_update_shared_vectors, qps_set_shared_*, qps_get_shared_equilibration); arrays validated by the caller.
 struct SharedFamilyOps {
     int family_rho = 0;               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule (one factor, hence one rho to move)
+    int column_rho = 0;               // qps_set_shared_column_rho: 1 every column moves its own rho (a path without a factor only: takes_column_rho)
     int warm_start = 0;               // qps_set_shared_warm_start: 0 z = y = 0, 1 the stored (z, y), 2 z = A x and the stored y
     int polish_on = 0;                // qps_set_shared_polish: 1 = every solve_batch ends with the polishing step on its own x and y
     std::vector<int> eq_kd, eq_ke;    // qps_set_shared_equilibration: D_j = 2^eq_kd[j], E_i = 2^eq_ke[i]; empty while off
     virtual ~SharedFamilyOps() {}
     virtual void update_vectors(const double* q, const double* l, const double* u) = 0;   // [count][n], [count][m], [count][m]; NULL keeps that array
+    virtual bool takes_column_rho() const { return false; }                               // rho is a multiplier of the path, not part of a factor
     virtual void set_rho_scale(const double* scale) = 0;                                  // [m], or NULL
     virtual void set_equilibration(int passes) = 0;                                       // 0..50
     virtual void set_dual(const double* z, const double* y) = 0;                          // [count][m] each, finite; NULL keeps that array

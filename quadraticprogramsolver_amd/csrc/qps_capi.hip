@@ -484,7 +484,25 @@ QPS_API int32_t qps_set_shared_adaptive_rho(qps_handle hh, int32_t mode) {
     if (mode != 0 && mode != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_adaptive_rho: mode must be 0 (fixed rho) or 1 (family-wide adaptive rho)");
     int rc; SharedFamilyOps* fam = shared_gate(h, "qps_set_shared_adaptive_rho", "run the family-wide rho rule", &rc);
     if (!fam) return rc;
+    if (mode && fam->column_rho)
+        return fail_with(h, QPS_ERR_UNSUPPORTED, "qps_set_shared_adaptive_rho: the per-column rule is on (turn qps_set_shared_column_rho off first); the handle is unchanged");
     fam->family_rho = mode;
+    return QPS_OK;
+}
+
+QPS_API int32_t qps_set_shared_column_rho(qps_handle hh, int32_t on) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (on != 0 && on != 1) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_set_shared_column_rho: on must be 0 (off) or 1 (every column moves its own rho)");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_set_shared_column_rho", "run the per-column rho rule", &rc);
+    if (!fam) return rc;
+    if (on && !fam->takes_column_rho())
+        return fail_with(h, QPS_ERR_UNSUPPORTED, "qps_set_shared_column_rho: one factor serves every column of a dense or sparse L D L' shared-matrix batch, so its columns "
+                                                 "cannot move rho one by one (qps_set_shared_adaptive_rho moves it for the family); only a matrix-free CG shared-matrix "
+                                                 "batch takes the per-column rule");
+    if (on && fam->family_rho)
+        return fail_with(h, QPS_ERR_UNSUPPORTED, "qps_set_shared_column_rho: the family-wide rule is on (turn qps_set_shared_adaptive_rho off first); the handle is unchanged");
+    fam->column_rho = on;
     return QPS_OK;
 }
 

@@ -237,6 +237,9 @@ template <typename T> struct CgPanelArgs {
     const int* active = nullptr;                 // one word per column
     const T *rho_row = nullptr, *rho1_row = nullptr;   // rho_i and 1 / rho_i per row of A while a scale is set (m long)
     T rho = T(1), sigma = T(0), alpha = T(0);
+    // qps_set_shared_column_rho: rho_b and 1 / rho_b per column (16 npanel long) instead of rho; rho_row / rho1_row then hold s_i and 1 / s_i and the kernels
+    // multiply.  NULL: the scalar rho, in the instantiations that never read these
+    const T *rho_col = nullptr, *rho1_col = nullptr;
     double eps_pcg = 0; int max_it = 0;          // abstol and maxiter of cg!
 };
 int cg_panel_op_spr(int64_t nnzP, int64_t nnzA, int n);   // from the mean of nnz(row of P) + nnz(row of A'): what one row group of the operator's second launch walks
@@ -250,6 +253,8 @@ template <typename T> void cg_panel_iteration(hipStream_t st, const CgPanelArgs<
 template <typename T> void cg_panel_finish(hipStream_t st, const CgPanelArgs<T>& a, int cur);   // the last ||r||^2 folded into state[cur] in place, before the host reads it
 // z~ = A x~ with SolveQuadraticProgram.jl:59-61 as its epilogue, then xp = x, x = alpha x~ + (1 - alpha) x; active columns only
 template <typename T> void cg_panel_post(hipStream_t st, const CgPanelArgs<T>& a);
+// w = rho_b z - y (rho_b s_i z - y with a row scale) on the active columns: panel_w with the rho of a.rho_col, which must be set
+template <typename T> void cg_panel_w(hipStream_t st, const CgPanelArgs<T>& a, T* w);
 
 // ---- small-problem path (k_small.hip): the whole loop in one single-workgroup launch ---------------------------------------
 template <typename T> bool admm_small_supported(int n, int m, int NP, int MP);

@@ -302,6 +302,10 @@ template <typename T> struct CgSharedBatchSolver final : CsrFamilySolver<T> {
     std::vector<int64_t> cg_total;         // per column, over the ADMM iterations of the running solve
     int last_cg = 0; double eps_pcg = 1e-6; int itr_pcg = 1000;
     int cat_rhs = 0, cat_it = 0, cat_post = 0;
+    // qps_set_shared_column_rho: rho_b in [0, CP), 1 / rho_b in [CP, 2 CP) (padding columns: 1), allocated at the first solve under the rule.  1 / rho_b is
+    // T(1) / T(rho_b), the division of the scalar path: a column that never switches runs the arithmetic of a fixed rho.  With a row scale the rows hold
+    // s_i and 1 / s_i (push_row_rho at base 1) and the kernels multiply: two roundings where the scalar path has one.
+    T* col_rho = nullptr; std::vector<T> h_col_rho;
 
     CgSharedBatchSolver(int dev, int cnt, int64_t n_, int64_t m_, CgSharedInput&& in, const double* qh, const double* lh, const double* uh)
         : B(dev, cnt, n_, m_, "a CG", std::move(in.Pcp), std::move(in.Pri), in.Pnz, std::move(in.Acp), std::move(in.Ari), in.Anz) {
@@ -335,6 +339,7 @@ template <typename T> struct CgSharedBatchSolver final : CsrFamilySolver<T> {
     void set_equilibration(int passes) override {
         if (passes > 0) throw QpsError(QPS_ERR_UNSUPPORTED, "CG shared-matrix batch: equilibration is not supported");
     }
+    bool takes_column_rho() const override { return true; }   // nothing is factorised: rho is a multiplier in three kernels
 
   protected:
     void check_params(const qps_params& p) override {
@@ -358,12 +363,20 @@ template <typename T> struct CgSharedBatchSolver final : CsrFamilySolver<T> {
     void switch_rho(double rho, double) override {
         if (!rho_scale.empty()) this->push_row_rho(rho);                                            // the operator and the row update read rho_i
     }
+    // one small upload, ordered on the stream: the three kernels read it from the next launch on (the uploader stages the host values before it returns)
+    void column_rho_changed(const std::vector<double>& rho_col) override {
+        if (!col_rho) { col_rho = mem.template dalloc<T>(2 * (int64_t)CP, st); h_col_rho.assign(2 * (size_t)CP, T(1)); }
+        for (int b = 0; b < count; ++b) { h_col_rho[b] = (T)rho_col[b]; h_col_rho[CP + b] = T(1) / h_col_rho[b]; }
+        this->up->copy(col_rho, h_col_rho.data(), sizeof(T) * h_col_rho.size());
+    }
     void iterate(int lvl, double rho, double sigma, double alpha) override {
-        const bool scaled = !rho_scale.empty();
+        const bool scaled = !rho_scale.empty(), percol = this->column_rho != 0;
         a.rho = (T)rho; a.sigma = (T)sigma; a.alpha = (T)alpha; a.rho_row = scaled ? rs_rho : nullptr; a.rho1_row = scaled ? rs_rho1 : nullptr;
+        a.rho_col = percol ? col_rho : nullptr; a.rho1_col = percol ? col_rho + CP : nullptr;
         {
             ProfScope ps(prof, cat_rhs, lvl);
-            panel_w<T>(st, z, y, d_active, a.rho_row, a.rho, (int)m, npanel, w);                    // LinearSystemSolvers.jl:176
+            if (percol) cg_panel_w<T>(st, a, w);                                                    // the same with rho_b (s_i) of the column
+            else panel_w<T>(st, z, y, d_active, a.rho_row, a.rho, (int)m, npanel, w);               // LinearSystemSolvers.jl:176
             cg_panel_begin<T>(st, a);                                                               // :177-178 and the head of cg!
         }
         HIPC(hipMemcpyAsync(h_state + CP, a.state, sizeof(CgPanelState) * (size_t)CP, hipMemcpyDeviceToHost, st));   // read at the first synchronisation

@@ -43,7 +43,8 @@ inline void require_same_pattern(const char* name, int64_t ncols, const std::vec
 
 // =================================================================================================================
 // What the three paths have in common: the resources, the state in 16-column panels [panel][rows][16] (rows = rowsN for n-vectors, rowsM for m-vectors), the
-// options, and the loop.  rho is common (a common factor needs a common rho): fixed, or moved for the whole family by qps_set_shared_adaptive_rho; every column
+// options, and the loop.  rho is common (a common factor needs a common rho): fixed, or moved for the whole family by qps_set_shared_adaptive_rho; on a path
+// without a factor (takes_column_rho) qps_set_shared_column_rho lets every column move its own rho by SolveQuadraticProgram.jl:47, :92-96.  Every column
 // keeps its own check, flag, stopping iteration and residuals, and a column that stopped is frozen by the active mask, exactly as BatchedDenseSolver does.
 // A path supplies its matrices, its factorisation and the hooks at the end of the class; a hook owns every launch of its step, in the path's own order.
 // =================================================================================================================
@@ -219,12 +220,12 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         HIPC(hipSetDevice(device));
         check_params(p);
         const double t0 = now_s();
-        if (family_rho && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
+        if ((family_rho || column_rho) && !(p.fctrRho > 0)) throw QpsError(QPS_ERR_BAD_ARGUMENT, "fctrRho must be positive");
         double rho = p.rho, rhorho = rho;                                                           // :43; rho moves under the family rule only
         const double sigma = p.sigma, alpha = p.alpha;
         const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma;
-        if (!rho_scale.empty()) push_row_rho(rho);
+        if (!rho_scale.empty()) push_row_rho(column_rho ? 1.0 : rho);                               // under the column rule the rows hold s_i, rho_b is the column's
         if (!reuse) { ProfScope ps(prof, cat_fac, 1); factor_at_setup(rho, sigma, p); }             // :36, once for all columns
         put_panels(xh, x, n, rowsN);
         if (kd) panel_rowscale<T>(st, x, kd, -1, rowsN, npanel, x);                                 // warm start in the scaled variables: x~ = D^-1 x
@@ -242,6 +243,8 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
         const double t1 = now_s();
         int nactive = count;
         std::vector<int> nref(count, 0); std::vector<double> rho_col(count, rho), prop_col(count, rho); double tref = 0;
+        const std::vector<int> alone(1, 1);                                                         // the mask of a family of one: the column rule's proposal
+        if (column_rho) column_rho_changed(rho_col);                                                // :43 for every column
         for (int ii = 1; ii <= p.numIterations && nactive > 0; ++ii) {                              // :45
             if (family_rho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {         // :47, once for the family
                 const double ta = now_s();
@@ -253,6 +256,17 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
                 for (int b = 0; b < count; ++b) if (active[b]) { ++nref[b]; rho_col[b] = rho; }
                 HIPC(hipStreamSynchronize(st));                                                     // tRefactor: host wall time until the device has finished the switch
                 tref += now_s() - ta;
+            }
+            if (column_rho) {                                                                       // :47, column by column; a column that stopped keeps its rho
+                bool moved = false;
+                for (int b = 0; b < count; ++b)
+                    if (active[b] && ((prop_col[b] * p.fctrRho < rho_col[b]) || (prop_col[b] > p.fctrRho * rho_col[b]))) { rho_col[b] = prop_col[b]; ++nref[b]; moved = true; }
+                if (moved) {
+                    const double ta = now_s();
+                    { ProfScope ps(prof, cat_switch, 1); column_rho_changed(rho_col); }
+                    HIPC(hipStreamSynchronize(st));
+                    tref += now_s() - ta;
+                }
             }
             const int lvl = (prof.level == 1 && ii % 50 == 13) ? 1 : 2;   // level 1: one sample of each category in 50 iterations
             const bool at_check = ii % p.numItrConv == 0;
@@ -285,6 +299,8 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
                 rhorho = family_rho_proposal(res_host, active, count, rho, rhorho);
                 for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = rhorho;
             }
+            if (column_rho)                                                                         // :92-96 from the column's own four norms, its stopping check included
+                for (int b = 0; b < count; ++b) if (active[b] || iters[b] == ii) prop_col[b] = family_rho_proposal(res_host + 8 * b, alone, 1, rho_col[b], prop_col[b]);
             if (any_done && nactive > 0) push_active();
         }
         HIPC(hipStreamSynchronize(st));
@@ -413,6 +429,9 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     // prepare the launch arguments of this solve.
     virtual void begin_solve(int warm, double rho, double sigma, double alpha) = 0;
     virtual void switch_rho(double rho, double sigma) = 0;                            // the family moved to `rho`: new factor, state that held the previous rho
+    // qps_set_shared_column_rho: column b runs on rho_col[b] from the next iteration on (at the start of a solve: every column on params.rho).  Only a path
+    // that answers takes_column_rho is ever asked; it leaves the host vector free when it returns.
+    virtual void column_rho_changed(const std::vector<double>& /*rho_col*/) {}
     virtual void iterate(int lvl, double rho, double sigma, double alpha) = 0;        // one ADMM iteration of every active column, profiled at level `lvl`
     // Ax = A xv, Px = P xv, Aty = A'yv for arbitrary panels (the check's x, y; the certificates' dx, dyh; the polishing step's v_x, mask v_lambda); usable outside a solve
     virtual void check_products(const T* xv, const T* yv) = 0;

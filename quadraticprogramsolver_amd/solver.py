@@ -381,6 +381,15 @@ class QuadraticProgramSharedBatch(_Handle):
         stays refused."""
         _lib.check(_lib.lib().qps_set_shared_adaptive_rho(self._h, 1 if on else 0), self._h)
 
+    def set_column_rho(self, on=True):
+        """Per-column adaptive ρ (qps_set_shared_column_rho), on ``QuadraticProgramCgSharedBatch``: every column moves its OWN ρ by the reference's rule
+        (SolveQuadraticProgram.jl:47, :92-96) from its own four norms, starting from ``ρ`` of every ``solve`` and switching on ``fctrΡ``; nothing is factorised
+        there, so a switch is one small upload.  A column then equals ``QuadraticProgram(..., linsys="cg", adptΡ=True)``; ``numRefactor`` / ``rhoFinal`` /
+        ``rhoProposed`` of the info dicts are the column's own.  The batch still runs until its slowest column.  ``False`` goes back to the fixed ρ.  The setting
+        stays with the handle and excludes ``set_adaptive_rho`` (turn the other off first).  The dense and the sparse L D L' handle refuse it with
+        QPS_ERR_UNSUPPORTED: one factor serves every column there."""
+        _lib.check(_lib.lib().qps_set_shared_column_rho(self._h, 1 if on else 0), self._h)
+
     def set_equilibration(self, passes=10):
         """Ruiz equilibration with exact powers of two (qps_set_shared_equilibration; OSQP §5.1), opt-in: ``passes`` = 1..50 passes of the rule, computed once for the
         family from mP and mA; ``0`` or ``None`` switches it off and restores the matrices bit for bit.  The loop runs on D P D, E A D, D q, E l, E u; warm starts,
@@ -536,7 +545,8 @@ class QuadraticProgramCgSharedBatch(QuadraticProgramSparseSharedBatch):
     ``QuadraticProgramSparseSharedBatch``.  Nothing is factorised: every iteration runs one CG per column, all columns in lockstep, the matrices read once per CG
     iteration for 16 columns.  Every column behaves as a stand-alone ``QuadraticProgram(..., linsys="cg")`` solve (matrix-free) with a fixed ρ and reports its
     own ``cgIterations``; ``adptΡ``, ``polish`` and a ``linsys`` other than "auto" / "cg" are refused with QPS_ERR_UNSUPPORTED, ``set_equilibration`` with a
-    positive pass count too.  Every other option of ``QuadraticProgramSharedBatch`` works as there; a ρ switch of ``set_adaptive_rho`` costs no factorisation."""
+    positive pass count too.  Every other option of ``QuadraticProgramSharedBatch`` works as there; a ρ switch of ``set_adaptive_rho`` costs no factorisation, and
+    ``set_column_rho`` gives every column the reference's per-problem adaptive ρ (a column then equals ``linsys="cg", adptΡ=True``)."""
 
     _create = "qps_create_csc_shared_batch_cg"
     _cg = (1e-6, 1000)
