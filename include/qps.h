@@ -458,6 +458,38 @@ int32_t qps_update_shared_matrices(qps_handle h, const double *P, int64_t ldp, c
 int32_t qps_update_shared_matrices_csc(qps_handle h, const int64_t *P_colptr, const int64_t *P_rowval, const double *P_nzval, const int64_t *A_colptr,
                                        const int64_t *A_rowval, const double *A_nzval, int32_t index_base);
 
+/* Values-only update of the sparse L D L' and the CG shared-matrix batch handle.  qps_update_shared_matrices_csc re-proves on the host, at every call, a pattern
+ * that is frozen by contract (conversion, field checks, transposition of P, canonical form, pattern comparison); these two entry points skip all of it: the caller
+ * reads the handle's canonical pattern once and from then on sends values only, in that order.  What still has to hold for VALUES is tested on the device.
+ * qps_get_shared_pattern: the canonical pattern the handle was created on -- 0-based, rows sorted inside every column, duplicates summed, explicit zeros kept.
+ * P_colptr and A_colptr have n + 1 elements, P_rowval *nnzP, A_rowval *nnzA; any output pointer may be NULL, so a first call sizes the arrays.  The pattern never
+ * changes.  QPS_ERR_BAD_ARGUMENT: a NULL handle; QPS_ERR_UNSUPPORTED: a dense shared-matrix batch (it stores no pattern), a handle that is not a shared-matrix
+ * batch.
+ * qps_update_shared_values: P_nzval[nnzP] and / or A_nzval[nnzA], entry k the value of entry k of that pattern.  A NULL matrix is kept and its count ignored; both
+ * NULL: QPS_OK, nothing changes, the factor stays valid.  location = QPS_MEM_HOST: host arrays, copied before the call returns.  location = QPS_MEM_DEVICE: the
+ * pointers are device memory on the handle's device (hipMalloc or an allocator on top of it); CONTRACT: the work that produced the values has completed before the
+ * call -- the handle copies them device to device on its own non-blocking stream, which is ordered against no stream of the caller (synchronise the producing
+ * stream, or wait for an event recorded on it, first).  The arrays are free again when the call returns.
+ * Tests, in the order of qps_update_shared_matrices_csc and with its codes and texts, so the same values are refused alike by both entry points: a count that
+ * is not the handle's (QPS_ERR_BAD_ARGUMENT, naming the matrix and both counts), a location other than 0 / 1 (QPS_ERR_BAD_ARGUMENT), with QPS_MEM_DEVICE a pointer
+ * that hipPointerGetAttributes does not call device memory of the handle's device (QPS_ERR_BAD_ARGUMENT, decided on the host before anything is enqueued); then, on
+ * the device, on the staged doubles and before any value array of the handle is touched: NaN / Inf in P, then in A (QPS_ERR_NOT_FINITE, "P contains NaN/Inf"),
+ * issymmetric(mP) with tolerance 0 -- entry (i, j) equals the stored entry (j, i), or equals 0 where (j, i) is not stored; the message names the column the host
+ * test names -- (QPS_ERR_BAD_ARGUMENT), and, on the L D L' handle while equilibrated, the range of the entries under the kept exponents (QPS_ERR_UNSUPPORTED).
+ * The host reads one verdict block (one copy, one synchronisation) and only then launches the value refresh of qps_update_shared_matrices_csc.
+ * Kept, stale, equilibration: exactly as qps_update_shared_matrices_csc -- every option, q, l, u, z, y, the analysis and the exponents stay; the numeric factor goes
+ * stale; certificates read zero until the next solve.  An updated handle equals, bit for bit, the handle that took the same values through
+ * qps_update_shared_matrices_csc.  The handle builds at its first call, and keeps, the position of every entry's transpose partner in P (nnzP ints).  The L D L'
+ * handle keeps its host copy of the values current (device input: one device-to-host copy of the committed doubles inside the call), so a later
+ * qps_set_shared_equilibration computes its exponents from the new matrices; the CG handle keeps no host values.
+ * After any refused call the handle is bit for bit what it was (the staging may hold the refused values).  The call returns with the handle's stream idle.
+ * QPS_ERR_UNSUPPORTED: a dense shared-matrix batch (use qps_update_shared_matrices), a handle that is not a shared-matrix batch.
+ * Out of scope: a mode without validation, a change of pattern, q / l / u or results in device memory, capturing the call in a graph. */
+#define QPS_MEM_HOST   0
+#define QPS_MEM_DEVICE 1
+int32_t qps_get_shared_pattern(qps_handle h, int64_t *nnzP, int64_t *nnzA, int64_t *P_colptr, int64_t *P_rowval, int64_t *A_colptr, int64_t *A_rowval);
+int32_t qps_update_shared_values(qps_handle h, const double *P_nzval, int64_t nnzP, const double *A_nzval, int64_t nnzA, int32_t location);
+
 /* The per-problem loop of RunBenchmarks.jl:88-104 sharded over the devices of ONE process ("one host thread + one stream per device", "work-stealing at
  * chunk boundaries").  `count` independent dense QPs of one shape, arrays stacked as for qps_create_dense_batch; `devices[num_workers]` lists the device of every worker
  * -- one host thread each; a device may be listed more than once (two workers sharing a card).  Every worker repeatedly takes the next range of QPs from a shared

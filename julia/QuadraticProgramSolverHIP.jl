@@ -440,6 +440,36 @@ function SharedBatchUpdateMatricesSparse!(sb::SharedBatchHip; mP::Union{Nothing,
     return nothing
 end
 
+# The canonical CSC pattern a SharedBatchCreateSparse / SharedBatchCreateCg handle was created on (qps_get_shared_pattern), as the library stores it: 0-BASED
+# colptr and rowval of mP and of mA, rows sorted inside every column, duplicates summed, explicit zeros kept.  nzval of sparse(...) of the same matrix is in
+# this order as long as it stores the same entries.  The pattern never changes.
+function SharedBatchPattern(sb::SharedBatchHip)
+    h = sb.h
+    nnz = zeros(Int64, 2)
+    null = Ptr{Int64}(C_NULL)
+    GC.@preserve nnz _check(ccall((:qps_get_shared_pattern, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                                  h, pointer(nnz, 1), pointer(nnz, 2), null, null, null, null), h)
+    vPcp, vPri, vAcp, vAri = zeros(Int64, sb.n + 1), zeros(Int64, nnz[1]), zeros(Int64, sb.n + 1), zeros(Int64, nnz[2])
+    GC.@preserve vPcp vPri vAcp vAri _check(ccall((:qps_get_shared_pattern, LIBQPS), Int32,
+        (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h, null, null, pointer(vPcp), pointer(vPri), pointer(vAcp), pointer(vAri)), h)
+    return vPcp, vPri, vAcp, vAri
+end
+
+# New values of mP and / or mA in the order of SharedBatchPattern (qps_update_shared_values): no pattern travels and none is compared; NaN / Inf, the symmetry
+# of mP (tolerance 0) and the range under kept exponents are tested on the device before the handle is touched, with the codes and messages of
+# SharedBatchUpdateMatricesSparse!, and the result equals that call's bit for bit.  nothing keeps that matrix.  Host vectors, or -- inDevice = true -- device
+# addresses (Ptr{Cvoid} of nnz Float64 each, memory of the handle's device, e.g. pointer(::ROCArray)): the work that produced them has to be complete before the
+# call, the handle copies them on its own stream.
+function SharedBatchUpdateValues!(sb::SharedBatchHip; vP::Union{Nothing, Vector{Float64}, Ptr{Cvoid}} = nothing, vA::Union{Nothing, Vector{Float64}, Ptr{Cvoid}} = nothing,
+    nnzP::Integer = vP isa Vector ? length(vP) : 0, nnzA::Integer = vA isa Vector ? length(vA) : 0, inDevice::Bool = false)
+    h = sb.h
+    (vP isa Vector || vA isa Vector) && inDevice && throw(ArgumentError("inDevice = true takes device addresses (Ptr{Cvoid}) and nnzP / nnzA"))
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : (a isa Ptr{Cvoid} ? a : Ptr{Cvoid}(pointer(a)))
+    GC.@preserve vP vA _check(ccall((:qps_update_shared_values, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32),
+                                    h, p(vP), Int64(nnzP), p(vA), Int64(nnzA), Int32(inDevice ? 1 : 0)), h)
+    return nothing
+end
+
 # Per-constraint ρ scale shared by all columns (qps_set_shared_rho_scale): row i runs with ρ_i = ρ vS[i]; vS has m finite, strictly positive entries.
 # nothing goes back to the scalar ρ.  Either way the next SharedBatchSolve! factorises, also with reuseFactor = true.
 function SharedBatchSetRhoScale!(sb::SharedBatchHip, vS::Union{Nothing, Vector{Float64}} = nothing)

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "qps_set_shared_adaptive_rho", "qps_set_shared_equilibration", "qps_get_shared_equilibration", "qps_set_shared_warm_start", "qps_set_shared_dual",
     "qps_set_shared_infeasibility", "qps_get_shared_certificate", "qps_polish_shared", "qps_set_shared_polish",
     "qps_create_csc_shared_batch_cg", "qps_update_shared_matrices", "qps_update_shared_matrices_csc", "qps_set_shared_column_rho",
+    "qps_get_shared_pattern", "qps_update_shared_values",
 ]
 
 QPS_OK = 0
@@ -33,6 +34,7 @@ STATUS_NAMES = {0: "QPS_OK", 1: "QPS_ERR_BAD_ARGUMENT", 2: "QPS_ERR_BAD_DIMENSIO
                 8: "QPS_ERR_UNSUPPORTED"}
 QPS_F64, QPS_F32 = 0, 1
 QPS_LINSYS_AUTO, QPS_LINSYS_CHOLESKY, QPS_LINSYS_CG, QPS_LINSYS_KKT_LDL, QPS_LINSYS_CG_EXPLICIT = 0, 1, 2, 3, 4
+QPS_MEM_HOST, QPS_MEM_DEVICE = 0, 1
 QPS_OP_P, QPS_OP_A, QPS_OP_AT, QPS_OP_PA, QPS_OP_REDUCED = 0, 1, 2, 3, 4
 
 
@@ -146,6 +148,8 @@ def lib() -> C.CDLL:
     L.qps_update_shared_vectors.argtypes = [hp, dp, dp, dp]
     L.qps_update_shared_matrices.argtypes = [hp, dp, i64, dp, i64]
     L.qps_update_shared_matrices_csc.argtypes = [hp, ip, ip, dp, ip, ip, dp, i32]
+    L.qps_get_shared_pattern.argtypes = [hp, ip, ip, ip, ip, ip, ip]
+    L.qps_update_shared_values.argtypes = [hp, C.c_void_p, i64, C.c_void_p, i64, i32]   # host or device addresses
     L.qps_set_shared_rho_scale.argtypes = [hp, dp]
     L.qps_set_shared_adaptive_rho.argtypes = [hp, i32]
     L.qps_set_shared_column_rho.argtypes = [hp, i32]

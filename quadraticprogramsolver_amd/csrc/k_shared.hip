@@ -390,6 +390,50 @@ __global__ __launch_bounds__(REFRESH_VALUES_THREADS) void k_refresh_values(const
     dst[k] = EXP ? eq_ldexp(v, e[k]) : v;
 }
 
+// The tests of qps_update_shared_values on the staged values of one matrix (validate_values in qps_kernels.h: the keys and what they mean).  Reads src and the
+// index arrays, writes nothing but the keys.  A lane past cnt stays in the kernel with neutral keys: the wave reductions want every lane.  The finite and the
+// symmetric key reduce only in a wave that has something to report (a wave-uniform branch); SYM false / EXP false: that test is not compiled in.
+template <typename T, bool SYM, bool EXP>
+__global__ __launch_bounds__(VALIDATE_VALUES_THREADS) void k_validate_values(const double* __restrict__ src, int64_t cnt, const int* __restrict__ partner,
+                                                                             const int* __restrict__ cp, const int* __restrict__ ri, int ncols,
+                                                                             const int* __restrict__ e, unsigned long long* __restrict__ verdict) {
+    constexpr int WAVES = VALIDATE_VALUES_THREADS / 64;
+    __shared__ unsigned long long part[VALIDATE_VERDICT_KEYS][WAVES];
+    const int64_t k = (int64_t)blockIdx.x * VALIDATE_VALUES_THREADS + threadIdx.x;
+    const bool in = k < cnt;
+    const double v = in ? src[k] : 0.0;
+    unsigned long long key[VALIDATE_VERDICT_KEYS] = {0, 0, 0, 0};
+    const bool nonfinite = !(fabs(v) <= 1.7976931348623157e308);
+    if (__ballot(nonfinite)) key[0] = wave_max_all_key(nonfinite ? ~0ull - (unsigned long long)k : 0ull);
+    if (SYM) {
+        bool off = false;
+        if (in) { const int p = partner[k]; off = p >= 0 ? v != src[p] : v != 0.0; }   // on the doubles, tolerance 0; -0.0 == 0.0
+        if (__ballot(off)) {
+            unsigned long long c = 0;
+            if (off) {
+                int lo = 0, hi = ncols;                                                 // the column of entry k: cp[lo] <= k < cp[lo + 1] (cp[ncols] = cnt > k)
+                while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if ((int64_t)cp[mid] <= k) lo = mid; else hi = mid; }
+                c = ~0ull - (unsigned long long)min(lo, ri[k]);
+            }
+            key[1] = wave_max_all_key(c);
+        }
+    }
+    if (EXP) {
+        const double a = in ? ldexp(fabs((double)(T)v), e[k]) : 0.0;                    // equil_range_add, entry for entry
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(a);
+        key[2] = wave_max_all_key(bits);
+        key[3] = wave_max_all_key(a > 0.0 ? ~0ull - bits : 0ull);
+    }
+    if ((threadIdx.x & 63) == 0)
+        for (int q = 0; q < VALIDATE_VERDICT_KEYS; ++q) part[q][threadIdx.x >> 6] = key[q];
+    __syncthreads();
+    if (threadIdx.x < VALIDATE_VERDICT_KEYS) {
+        unsigned long long best = 0;
+        for (int w = 0; w < WAVES; ++w) best = key_max(best, part[threadIdx.x][w]);
+        if (best) atomicMax(verdict + threadIdx.x, best);
+    }
+}
+
 __device__ __forceinline__ double sh_jmax(double a, double b) { return (isnan(a) || isnan(b)) ? (double)NAN : (a > b ? a : b); }
 
 // the decision of k_check_decide for every active column (fixed rho: the proposal stays rho); res: 8 doubles per column
@@ -726,8 +770,20 @@ template <typename T> void refresh_values(hipStream_t st, const double* src, con
     else if (e) hipLaunchKernelGGL((k_refresh_values<T, false, true>), grid, block, 0, st, src, map, e, cnt, dst);
     else hipLaunchKernelGGL((k_refresh_values<T, false, false>), grid, block, 0, st, src, map, e, cnt, dst);
 }
+template <typename T>
+void validate_values(hipStream_t st, const double* src, int64_t cnt, const int* partner, const int* cp, const int* ri, int ncols, const int* e,
+                     unsigned long long* verdict) {
+    if (cnt <= 0) return;
+    const dim3 grid((unsigned)((cnt + VALIDATE_VALUES_THREADS - 1) / VALIDATE_VALUES_THREADS)), block(VALIDATE_VALUES_THREADS);
+    if (partner && e) hipLaunchKernelGGL((k_validate_values<T, true, true>), grid, block, 0, st, src, cnt, partner, cp, ri, ncols, e, verdict);
+    else if (partner) hipLaunchKernelGGL((k_validate_values<T, true, false>), grid, block, 0, st, src, cnt, partner, cp, ri, ncols, e, verdict);
+    else if (e) hipLaunchKernelGGL((k_validate_values<T, false, true>), grid, block, 0, st, src, cnt, partner, cp, ri, ncols, e, verdict);
+    else hipLaunchKernelGGL((k_validate_values<T, false, false>), grid, block, 0, st, src, cnt, partner, cp, ri, ncols, e, verdict);
+}
 
 #define INST(T)                                                                                                                         \
+    template void validate_values<T>(hipStream_t, const double*, int64_t, const int*, const int*, const int*, int, const int*,          \
+                                     unsigned long long*);                                                                              \
     template void equil_rownorm<T>(hipStream_t, const T*, int, int, const int*, const int*, double*, double*);                          \
     template void scale_two_sided<T>(hipStream_t, T*, int, int, const int*, const int*, int);                                           \
     template void panel_rowscale<T>(hipStream_t, const T*, const int*, int, int, int, T*);                                              \

@@ -11,6 +11,13 @@ namespace qps {
 // One matrix of qps_update_shared_matrices_csc after layout::canonical_csc (0-based, rows sorted, duplicates summed); given == false keeps the handle's matrix
 struct CanonicalCsc { bool given = false; std::vector<int64_t> cp, ri; std::vector<double> nz; };
 
+// What the device found in the staged values of qps_update_shared_values, in the order the host tests of qps_update_shared_matrices_csc run in
+struct ValuesVerdict {
+    const char* not_finite = nullptr;    // "P" / "A": the first matrix that holds a NaN or an Inf
+    int64_t asymmetric_column = -1;      // the column layout::csc_asymmetry names for these values of P
+    bool refused() const { return not_finite || asymmetric_column >= 0; }
+};
+
 // What only the shared-matrix batches take (qps_update_shared_vectors, qps_set_shared_*, qps_get_shared_equilibration); arrays validated by the caller.
 struct SharedFamilyOps {
     int family_rho = 0;               // qps_set_shared_adaptive_rho: 0 fixed rho, 1 the family rule (one factor, hence one rho to move)
@@ -34,6 +41,12 @@ struct SharedFamilyOps {
     virtual bool takes_csc() const = 0;
     virtual void update_matrices(const double* P, int64_t ldp, const double* A, int64_t lda) = 0;   // column-major, NULL keeps that matrix
     virtual void update_matrices_csc(const CanonicalCsc& P, const CanonicalCsc& A) = 0;             // pattern compared with the handle's, entry for entry
+    // qps_get_shared_pattern: the canonical pattern of a path that takes CSC (the dense path refuses); any output may be NULL
+    virtual void get_pattern(int64_t* nnzP, int64_t* nnzA, int64_t* Pcp, int64_t* Pri, int64_t* Acp, int64_t* Ari) = 0;
+    // qps_update_shared_values: new values in the order of that pattern, from host (location 0) or device memory (1); NULL keeps that matrix.  The values are
+    // staged and tested on the device before anything of the handle is touched.  A verdict other than the default one is a refusal that qps_capi.hip words with
+    // the texts of the creators (nothing was modified); every other refusal is thrown.
+    virtual ValuesVerdict update_values(const double* P, int64_t nnzP, const double* A, int64_t nnzA, int location) = 0;
 };
 
 struct BatchSolverBase {

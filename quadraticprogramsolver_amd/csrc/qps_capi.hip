@@ -465,6 +465,34 @@ QPS_API int32_t qps_update_shared_matrices_csc(qps_handle hh, const int64_t* Pcp
     });
 }
 
+QPS_API int32_t qps_get_shared_pattern(qps_handle hh, int64_t* nnzP, int64_t* nnzA, int64_t* Pcp, int64_t* Pri, int64_t* Acp, int64_t* Ari) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_get_shared_pattern", "keep the canonical pattern they were created on", &rc);
+    if (!fam) return rc;
+    return guarded(h, [&] { fam->get_pattern(nnzP, nnzA, Pcp, Pri, Acp, Ari); });                     // the dense path words its own refusal
+}
+
+QPS_API int32_t qps_update_shared_values(qps_handle hh, const double* Pnz, int64_t nnzP, const double* Anz, int64_t nnzA, int32_t location) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_update_shared_values", "take new values on the pattern they keep", &rc);
+    if (!fam) return rc;
+    if (fam->takes_csc() && location != QPS_MEM_HOST && location != QPS_MEM_DEVICE)
+        return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_update_shared_values: location must be QPS_MEM_HOST (0) or QPS_MEM_DEVICE (1)");
+    ValuesVerdict v;
+    if (const int c = guarded(h, [&] { v = fam->update_values(Pnz, nnzP, Anz, nnzA, location); })) return c;   // (the dense path words its own refusal)
+    // what the device found is worded by the host code of qps_update_shared_matrices_csc: the same values, the same code and text from both entry points
+    if (v.not_finite) {
+        static const int64_t cp1[2] = {0, 1}, ri1[1] = {0};
+        const double nan1[1] = {std::numeric_limits<double>::quiet_NaN()};
+        const bool isA = v.not_finite[0] == 'A';                                                      // validate_csc's code and text for that matrix
+        return check_csc_matrices(1, 1, isA ? nullptr : cp1, ri1, nan1, isA ? cp1 : nullptr, ri1, nan1, 0, h);
+    }
+    if (v.asymmetric_column >= 0) return fail_asymmetric(v.asymmetric_column, h);
+    return QPS_OK;
+}
+
 QPS_API int32_t qps_set_shared_rho_scale(qps_handle hh, const double* scale) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");

@@ -181,6 +181,20 @@ template <typename T> void scale_entries(hipStream_t st, T* v, const int* e, int
 // (qps_update_shared_matrices_csc); rounded to T first, scaled afterwards.  map == NULL: src[k]; e == NULL: no scaling.  One entry per lane.
 constexpr int REFRESH_VALUES_THREADS = 256;
 template <typename T> void refresh_values(hipStream_t st, const double* src, const int* map, const int* e, int64_t cnt, T* dst);
+// validate_values: what has to hold for the staged canonical CSC values src[0, cnt) of one matrix before a values-only update may touch the handle
+// (qps_update_shared_values), decided on the device.  It reads the staging and the index arrays only and writes VALIDATE_VERDICT_KEYS keys into `verdict`
+// (zeroed by the caller; every key is a maximum over the entries, so the order of the workgroups does not matter; 0: nothing to report):
+//   [0] finite      ~0 - k of the first k whose value is NaN / Inf
+//   [1] symmetric   partner != NULL (P): ~0 - c, c the smallest min(i, j) over the entries k = (i, j) that differ from src[partner[k]] -- from 0.0 where
+//                   partner[k] < 0 -- which is the column layout::csc_asymmetry names.  cp / ri: the pattern as int arrays (the CSR copy of P), ncols columns
+//   [2], [3] range  e != NULL: the bits of the largest a = |(T) src[k]| 2^e[k], and ~0 - the bits of the smallest non-zero one (non-negative doubles order as
+//                   their bits do): what equil_check_range asks for
+// One entry per lane; a wave and then the workgroup reduce first, one atomic per key and workgroup.
+constexpr int VALIDATE_VALUES_THREADS = 256;
+constexpr int VALIDATE_VERDICT_KEYS = 4;
+template <typename T>
+void validate_values(hipStream_t st, const double* src, int64_t cnt, const int* partner, const int* cp, const int* ri, int ncols, const int* e,
+                     unsigned long long* verdict);
 // out[panel][r][16] = sum_k M[r][k] B[panel][k][16] for a plain CSR matrix (k_csr_panel.hip): the check's products of the sparse shared batch.  One 16-lane
 // row per (matrix row, panel), spr strips of it for long rows (csr_panel_spr: from the mean row length), fixed summation order, no atomics.
 // rowsB / rowsOut: rows per panel of B / out.

@@ -1,7 +1,10 @@
 // qps_shared_csr.hip -- the two paths of the shared-matrix batches that are created from CSC arrays, under the family driver of qps_shared_family.h:
-// CsrFamilySolver (the three CSR copies the check reads, the frozen pattern, qps_update_shared_matrices_csc), the sparse KKT L D L' with panel sweeps
+// CsrFamilySolver (the three CSR copies the check reads, the frozen pattern, qps_update_shared_matrices_csc and the values-only qps_update_shared_values with its
+// tests on the device), the sparse KKT L D L' with panel sweeps
 // (SparseSharedBatchSolver, k_ldl.hip, k_csr_panel.hip) and the matrix-free CG on panels (CgSharedBatchSolver, k_cg_panel.hip).
 // qps_capi.hip validates the caller's arrays and builds the handles through the two factories at the end of this file.
+#include <cstring>
+
 #include "qps_ldl.h"
 #include "qps_shared_family.h"
 
@@ -21,6 +24,10 @@ template <typename T> struct CsrFamilySolver : SharedFamilySolver<T> {
     // qps_update_shared_matrices_csc, from its first call on: the staging of the canonical values (nnz(P) + nnz(A) doubles) and the position of every entry of
     // the by-rows copy of A in CSC order
     double* upd_src = nullptr; int* upd_map = nullptr;
+    // qps_update_shared_values, from its first call on: where the transpose partner of every entry of P is stored (-1: nowhere), the verdict block of
+    // validate_values for P and for A on the device and pinned, and the three profiling categories of the call
+    int* upd_partner = nullptr; unsigned long long *upd_verdict = nullptr, *h_verdict = nullptr;
+    int cat_upd_stage = 0, cat_upd_check = 0, cat_upd_refresh = 0;
     const char* const path_word;   // "a sparse", "a CG": how the refusal of the dense form names the path
 
     CsrFamilySolver(int dev, int cnt, int64_t n_, int64_t m_, const char* word, std::vector<int64_t>&& Pcp, std::vector<int64_t>&& Pri, const std::vector<double>& Pnz,
@@ -62,28 +69,137 @@ template <typename T> struct CsrFamilySolver : SharedFamilySolver<T> {
         if (Pc.given && np > 0) {
             up->copy(upd_src, Pc.nz.data(), sizeof(double) * (size_t)np);
             refresh_values<T>(st, upd_src, nullptr, eP, np, const_cast<T*>(P.va));
-            values_replaced(false, upd_src, eK, Pc.nz);
+            values_replaced(false, upd_src, eK, np, Pc.nz.data());
         }
         if (Ac.given && na > 0) {
             up->copy(upd_src + np, Ac.nz.data(), sizeof(double) * (size_t)na);
             refresh_values<T>(st, upd_src + np, upd_map, eA, na, const_cast<T*>(A.va));
             refresh_values<T>(st, upd_src + np, nullptr, eAt, na, const_cast<T*>(At.va));
-            values_replaced(true, upd_src + np, eK ? eK + np : nullptr, Ac.nz);
+            values_replaced(true, upd_src + np, eK ? eK + np : nullptr, na, Ac.nz.data());
         }
         HIPC(hipStreamSynchronize(st));
         factor_valid = false;                                      // the next solve runs the path's setup on the new values, also with reuseFactor
         this->last_conv.clear();
     }
+    void get_pattern(int64_t* np, int64_t* na, int64_t* Pcp, int64_t* Pri, int64_t* Acp, int64_t* Ari) override {
+        if (np) *np = nnzP();
+        if (na) *na = nnzA();
+        if (Pcp) std::copy(hPcp.begin(), hPcp.end(), Pcp);
+        if (Pri) std::copy(hPri.begin(), hPri.end(), Pri);
+        if (Acp) std::copy(hAcp.begin(), hAcp.end(), Acp);
+        if (Ari) std::copy(hAri.begin(), hAri.end(), Ari);
+    }
+    // New values in the order of the frozen pattern, nothing else from the caller: the host looks at the two counts and, for device input, at the pointer
+    // attributes; the values go into the staging (an upload, or a device-to-device copy on the handle's stream) and validate_values tests them there -- finite,
+    // issymmetric(mP) with tolerance 0, the range under kept exponents -- into one verdict block that the host reads with one copy and one synchronisation.
+    // Only a clean verdict reaches the launches of update_matrices_csc.  upd_partner (the transpose partner of every entry of P) and the verdict block are
+    // built at the first call and kept, like upd_src and upd_map; they and the staging are all a refused call leaves behind.
+    ValuesVerdict update_values(const double* Pv, int64_t cntP, const double* Av, int64_t cntA, int location) override {
+        const int64_t np = nnzP(), na = nnzA();
+        auto count_is = [](const char* name, int64_t got, int64_t want) {
+            if (got == want) return;
+            char b[192];
+            snprintf(b, sizeof b, "qps_update_shared_values: nnz%s is %lld, the handle's %s has %lld stored entries; the handle is unchanged", name, (long long)got,
+                     name, (long long)want);
+            throw QpsError(QPS_ERR_BAD_ARGUMENT, b);
+        };
+        if (Pv) count_is("P", cntP, np);
+        if (Av) count_is("A", cntA, na);
+        if (!Pv && !Av) return {};
+        HIPC(hipSetDevice(device));
+        // device input: what the pointers are is decided here, on the host, before anything is enqueued
+        if (location == QPS_MEM_DEVICE) {
+            if (Pv && np > 0) require_device_memory("P_nzval", Pv);
+            if (Av && na > 0) require_device_memory("A_nzval", Av);
+        }
+        HIPC(hipStreamSynchronize(st));
+        if (!upd_src) upd_src = mem.template dalloc<double>(np + na, st);
+        if (!upd_map) {
+            const std::vector<int> map = layout::csc_rows_position_map(m, n, hAcp, hAri);
+            upd_map = mem.template dalloc<int>(na, st);
+            if (na > 0) up->copy(upd_map, map.data(), sizeof(int) * (size_t)na);
+        }
+        if (!upd_partner) {
+            const std::vector<int> map = layout::csc_transpose_partner_map(n, hPcp, hPri);
+            upd_partner = mem.template dalloc<int>(np, st);
+            if (np > 0) up->copy(upd_partner, map.data(), sizeof(int) * (size_t)np);
+            upd_verdict = mem.template dalloc<unsigned long long>(2 * VALIDATE_VERDICT_KEYS, st);
+            h_verdict = mem.template pinned<unsigned long long>(2 * VALIDATE_VERDICT_KEYS);
+            cat_upd_stage = prof.category("shared values: staging (upload / device copy)", 8.0 * (np + na));
+            cat_upd_check = prof.category("shared values: validation + verdict", 8.0 * (np + na));
+            cat_upd_refresh = prof.category("shared values: refresh of the value arrays", (8.0 + sizeof(T)) * (np + 2.0 * na));
+        }
+        const int* eK = update_exponents();
+        const int *eP = eK ? eK + np + na : nullptr, *eA = eK ? eP + np : nullptr, *eAt = eK ? eA + na : nullptr;
+        const bool doP = Pv && np > 0, doA = Av && na > 0;
+        {
+            ProfScope ps(prof, cat_upd_stage, 1);
+            if (doP) stage_values(upd_src, Pv, np, location);
+            if (doA) stage_values(upd_src + np, Av, na, location);
+        }
+        {
+            ProfScope ps(prof, cat_upd_check, 1);
+            HIPC(hipMemsetAsync(upd_verdict, 0, sizeof(unsigned long long) * 2 * VALIDATE_VERDICT_KEYS, st));
+            if (doP) validate_values<T>(st, upd_src, np, upd_partner, P.rp, P.ci, (int)n, eK, upd_verdict);
+            if (doA) validate_values<T>(st, upd_src + np, na, nullptr, nullptr, nullptr, (int)n, eK ? eK + np : nullptr, upd_verdict + VALIDATE_VERDICT_KEYS);
+            HIPC(hipMemcpyAsync(h_verdict, upd_verdict, sizeof(unsigned long long) * 2 * VALIDATE_VERDICT_KEYS, hipMemcpyDeviceToHost, st));
+        }
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+        // the verdict, in the order of the host tests of update_matrices_csc: finite (P, then A), symmetric, range
+        const unsigned long long *vP = h_verdict, *vA = h_verdict + VALIDATE_VERDICT_KEYS;
+        ValuesVerdict verdict;
+        if (vP[0] || vA[0]) { verdict.not_finite = vP[0] ? "P" : "A"; return verdict; }
+        if (vP[1]) { verdict.asymmetric_column = (int64_t)(~0ull - vP[1]); return verdict; }
+        if (eK) {
+            auto as_double = [](unsigned long long b) { double d; std::memcpy(&d, &b, sizeof d); return d; };
+            const double hi = as_double(std::max(vP[2], vA[2]));
+            const unsigned long long lk = std::max(vP[3], vA[3]);
+            equil_check_range<T>(hi, lk ? as_double(~0ull - lk) : INFINITY, "qps_update_shared_values");
+        }
+        {
+            ProfScope ps(prof, cat_upd_refresh, 1);
+            if (doP) {
+                refresh_values<T>(st, upd_src, nullptr, eP, np, const_cast<T*>(P.va));
+                values_replaced(false, upd_src, eK, np, location == QPS_MEM_HOST ? Pv : nullptr);
+            }
+            if (doA) {
+                refresh_values<T>(st, upd_src + np, upd_map, eA, na, const_cast<T*>(A.va));
+                refresh_values<T>(st, upd_src + np, nullptr, eAt, na, const_cast<T*>(At.va));
+                values_replaced(true, upd_src + np, eK ? eK + np : nullptr, na, location == QPS_MEM_HOST ? Av : nullptr);
+            }
+        }
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+        factor_valid = false;
+        this->last_conv.clear();
+        return verdict;
+    }
 
   protected:
-    // The three hooks of update_matrices_csc; the CG path leaves them as they are.
+    // QPS_MEM_DEVICE: "device memory, this device" by the pointer attributes, or QPS_ERR_BAD_ARGUMENT.  Host code only; nothing is enqueued.
+    void require_device_memory(const char* name, const double* p) const {
+        hipPointerAttribute_t at;
+        const hipError_t rc = hipPointerGetAttributes(&at, p);
+        if (rc != hipSuccess) (void)hipGetLastError();             // an unregistered host pointer is an error of that call on some runtimes: not a sticky one
+        if (rc == hipSuccess && at.type == hipMemoryTypeDevice && at.device == device) return;
+        throw QpsError(QPS_ERR_BAD_ARGUMENT, std::string("qps_update_shared_values: ") + name + " is not device memory on the handle's device (location = "
+                                             "QPS_MEM_DEVICE); the handle is unchanged");
+    }
+    // cnt doubles into the staging, ordered on the handle's stream: through the uploader, or device to device (the caller's work on them has completed)
+    void stage_values(double* dst, const double* src, int64_t cnt, int location) {
+        if (location == QPS_MEM_HOST) up->copy(dst, src, sizeof(double) * (size_t)cnt);
+        else HIPC(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToDevice, st));
+    }
+    // The three hooks of update_matrices_csc and update_values; the CG path leaves them as they are.
     // Before anything is modified, and before any allocation or upload: the path's refusal of the new values (the pattern has been compared)
     virtual void check_new_values(const CanonicalCsc&, const CanonicalCsc&) {}
     // One exponent per entry, on the device, in the order of the value arrays -- the factor's [P; A] in CSC order, then the CSR copies P, A, A' -- or null
     virtual const int* update_exponents() { return nullptr; }
-    // The refresh of the CSR copies of P (isA false) or A with the new values `nz` is on the stream: src is their staging on the device in CSC order, e the
-    // exponents of that block of the factor's values or null.  Called for a matrix that was given and has entries.
-    virtual void values_replaced(bool /*isA*/, const double* /*src*/, const int* /*e*/, const std::vector<double>& /*nz*/) {}
+    // The refresh of the CSR copies of P (isA false) or A with `cnt` new values is on the stream: src is their staging on the device in CSC order, e the
+    // exponents of that block of the factor's values or null, host the same values in host memory or null (they came from device memory: a path that keeps
+    // host copies fetches them from src).  Called for a matrix that was given and has entries.
+    virtual void values_replaced(bool /*isA*/, const double* /*src*/, const int* /*e*/, int64_t /*cnt*/, const double* /*host*/) {}
     // what both begin_solve end their clearing with: OSQP's warm_start(x, y) in mode 2, z = A x~ without projection, then the mask
     void start_columns(int warm) {
         if (warm == 2) { ProfScope ps(prof, cat_start, 1); csr_panel<T>(st, A, x, (int)n, z, (int)m, npanel); }
@@ -261,9 +377,13 @@ template <typename T> struct SparseSharedBatchSolver final : CsrFamilySolver<T> 
         }
         return upd_e;
     }
-    void values_replaced(bool isA, const double* src, const int* e, const std::vector<double>& nz) override {
-        ldl->set_values(src, e, isA ? this->nnzP() : 0, (int64_t)nz.size());
-        (isA ? hAnz : hPnz) = nz;            // what a later qps_set_shared_equilibration computes its exponents from
+    void values_replaced(bool isA, const double* src, const int* e, int64_t cnt, const double* host) override {
+        ldl->set_values(src, e, isA ? this->nnzP() : 0, cnt);
+        // what a later qps_set_shared_equilibration computes its exponents from: kept current at every committed update -- device input is copied back here,
+        // not fetched when the scaling next asks (the staging is scratch: a refused update in between may have overwritten it)
+        std::vector<double>& keep = isA ? hAnz : hPnz;
+        if (host) keep.assign(host, host + cnt);
+        else HIPC(hipMemcpyAsync(keep.data(), src, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, st));   // complete at the update's closing synchronisation
     }
     void begin_solve(int warm, double, double, double) override {
         this->reset_state(warm);             // from mode 1 on the first right-hand side is built from the z and y that stay (rhs_ready)

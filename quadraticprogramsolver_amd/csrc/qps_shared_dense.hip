@@ -63,6 +63,12 @@ template <typename T> struct SharedBatchSolver final : SharedFamilySolver<T> {
     void update_matrices_csc(const CanonicalCsc&, const CanonicalCsc&) override {
         throw QpsError(QPS_ERR_UNSUPPORTED, "qps_update_shared_matrices_csc: a dense shared-matrix batch takes its matrices through qps_update_shared_matrices");
     }
+    void get_pattern(int64_t*, int64_t*, int64_t*, int64_t*, int64_t*, int64_t*) override {
+        throw QpsError(QPS_ERR_UNSUPPORTED, "qps_get_shared_pattern: a dense shared-matrix batch stores no sparsity pattern");
+    }
+    ValuesVerdict update_values(const double*, int64_t, const double*, int64_t, int) override {
+        throw QpsError(QPS_ERR_UNSUPPORTED, "qps_update_shared_values: a dense shared-matrix batch takes its matrices through qps_update_shared_matrices");
+    }
     // New P and / or A (column-major, validated by the caller) into the storage of the old ones, scaled by the kept exponents while the equilibration is on; q, l,
     // u, z, y, every option and every allocation stay.  The range of the scaled entries is checked on the host before the first upload.
     void update_matrices(const double* Ph, int64_t ldp, const double* Ah, int64_t lda) override {

@@ -104,6 +104,22 @@ std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::
     return map;
 }
 
+std::vector<int> csc_transpose_partner_map(int64_t n, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri) {
+    const int64_t nnz = cp[(size_t)n];
+    if (nnz > 2000000000LL || n > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");
+    std::vector<int> map((size_t)nnz);
+    std::vector<int64_t> cur(cp.begin(), cp.end() - 1);   // per column i: the first entry whose row has not been passed yet
+    // columns j visited in order: the rows column i is asked for only grow, so every cursor moves forward only -- O(nnz) in all
+    for (int64_t j = 0; j < n; ++j)
+        for (int64_t k = cp[(size_t)j]; k < cp[(size_t)j + 1]; ++k) {
+            const int64_t i = ri[(size_t)k];
+            int64_t& c = cur[(size_t)i];
+            while (c < cp[(size_t)i + 1] && ri[(size_t)c] < j) ++c;
+            map[(size_t)k] = c < cp[(size_t)i + 1] && ri[(size_t)c] == j ? (int)c : -1;
+        }
+    return map;
+}
+
 CsrHost csc_as_transposed_csr(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz) {
     const int64_t nnz = cp[(size_t)ncols];
     if (nnz > 2000000000LL || nrows > 2000000000LL || ncols > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");

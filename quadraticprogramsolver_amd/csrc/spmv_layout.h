@@ -45,6 +45,9 @@ void csc_to_csr_pair(int64_t nrows, int64_t ncols, const std::vector<int64_t>& c
 // Where the by-rows copy of csc_to_csr_pair took its values from: rows.va[k] == nz[map[k]], map a permutation of [0, nnz).  What a value refresh on a frozen
 // pattern needs (qps_update_shared_matrices_csc); the pattern alone decides it.
 std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri);
+// Where the transpose partner of every entry of a canonical square CSC pattern is stored: entry k = (i, j) -> the position of (j, i), -1 where (j, i) is not
+// stored; a diagonal entry is its own partner.  What the symmetry test of a values-only update reads (qps_update_shared_values); the pattern alone decides it.
+std::vector<int> csc_transpose_partner_map(int64_t n, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri);
 // The CSC arrays of a canonical matrix (nrows x ncols) read as the CSR of its transpose (ncols x nrows) -- for a symmetric P that is P itself.
 CsrHost csc_as_transposed_csr(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz);
 // [top; bottom] stacked (same column count)

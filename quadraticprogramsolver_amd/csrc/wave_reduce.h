@@ -48,6 +48,27 @@ template <typename T> __device__ __forceinline__ T wave_max_all_nonneg(T a) {
     t = fmax(t, dpp_get<0x143, 0xc, 0xf>(t));
     return lane_get(t, 63);
 }
+// the same for unsigned 64-bit keys (a lane without a DPP source contributes 0): minima and maxima of indices and of the bits of non-negative doubles
+template <int CTRL, int ROW_MASK, int BANK_MASK> __device__ __forceinline__ unsigned long long dpp_get(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROW_MASK, BANK_MASK, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, BANK_MASK, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long lane_get(unsigned long long v, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long key_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned long long wave_max_all_key(unsigned long long a) {
+    unsigned long long t = key_max(a, dpp_get<0x111, 0xf, 0xf>(a));
+    t = key_max(t, dpp_get<0x112, 0xf, 0xf>(a));
+    t = key_max(t, dpp_get<0x113, 0xf, 0xf>(a));
+    t = key_max(t, dpp_get<0x114, 0xf, 0xe>(t));
+    t = key_max(t, dpp_get<0x118, 0xf, 0xc>(t));
+    t = key_max(t, dpp_get<0x142, 0xa, 0xf>(t));
+    t = key_max(t, dpp_get<0x143, 0xc, 0xf>(t));
+    return lane_get(t, 63);
+}
 // sum of lanes 0..7 (other lanes ignored), returned in every lane
 template <typename T> __device__ __forceinline__ T lanes8_sum_all(T a) {
     T t = a + dpp_get<0x111, 0xf, 0xf>(a);

@@ -501,6 +501,7 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
         if getattr(mP, "ndim", 0) != 2 or getattr(mA, "ndim", 0) != 2:
             raise ValueError("mP and mA must be matrices")
         self.n, self.m = mP.shape[0], mA.shape[0]
+        self._device = int(device)                                 # update_values holds device tensors against it
         q = np.ascontiguousarray(np.atleast_2d(np.asarray(mQ, dtype=np.float64)))
         self.count = q.shape[0]
         l, u = self._rows(mL, "mL", self.m), self._rows(mU, "mU", self.m)
@@ -532,6 +533,51 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
         Acp, Ari, Anz = (None, None, None) if mA is None else self._csc(mA)
         ip, dp = (lambda a: None if a is None else _ip(a)), (lambda a: None if a is None else _dp(a))
         _lib.check(_lib.lib().qps_update_shared_matrices_csc(self._h, ip(Pcp), ip(Pri), dp(Pnz), ip(Acp), ip(Ari), dp(Anz), 0), self._h)
+
+    def pattern(self):
+        """``(P_indptr, P_indices, A_indptr, A_indices)`` as int64 arrays (qps_get_shared_pattern): the canonical CSC pattern the handle was created on -- 0-based,
+        rows sorted inside every column, duplicates summed, explicit zeros kept.  It never changes; ``update_values`` takes its values in this order."""
+        L = _lib.lib()
+        nP, nA = C.c_int64(), C.c_int64()
+        _lib.check(L.qps_get_shared_pattern(self._h, C.byref(nP), C.byref(nA), None, None, None, None), self._h)
+        Pcp, Pri = np.zeros(self.n + 1, dtype=np.int64), np.zeros(nP.value, dtype=np.int64)
+        Acp, Ari = np.zeros(self.n + 1, dtype=np.int64), np.zeros(nA.value, dtype=np.int64)
+        _lib.check(L.qps_get_shared_pattern(self._h, None, None, _ip(Pcp), _ip(Pri), _ip(Acp), _ip(Ari)), self._h)
+        return Pcp, Pri, Acp, Ari
+
+    def update_values(self, vP=None, vA=None):
+        """New values of ``mP`` and / or ``mA`` on the stored pattern, in the order of ``pattern()`` (qps_update_shared_values; ``None`` keeps that matrix): the
+        host passes of ``update_matrices`` over a pattern that cannot have changed are skipped, and what has to hold for values -- finite, ``mP`` symmetric with
+        tolerance 0, the range under kept exponents -- is tested on the device before the handle is touched, with the codes and messages of
+        ``update_matrices``.  Each of ``vP``, ``vA`` is anything ``np.asarray(..., float64)`` makes a vector of, or a ``torch.Tensor`` that is float64,
+        contiguous and on the handle's device, whose memory the library reads in place (torch's current stream on that device is synchronised first); both
+        given, they are both host arrays or both tensors.  The result equals ``update_matrices`` on the same values bit for bit."""
+        tensors = [type(v).__module__.split(".")[0] == "torch" for v in (vP, vA) if v is not None]
+        if any(tensors) and not all(tensors):
+            raise ValueError("vP and vA must both be host arrays or both be torch tensors")
+        device = bool(tensors) and tensors[0]
+        if device:
+            import torch                                                   # only here: host input never needs it
+            dev = self._device
+            for v, name in ((vP, "vP"), (vA, "vA")):
+                if v is None:
+                    continue
+                if v.dtype != torch.float64:
+                    raise ValueError(f"{name} must be a float64 tensor, not {v.dtype}")
+                if v.device.type != "cuda" or v.device.index != dev:
+                    raise ValueError(f"{name} must be on the handle's device cuda:{dev}, not {v.device}")
+                if v.dim() != 1 or not v.is_contiguous():
+                    raise ValueError(f"{name} must be a contiguous vector")
+            torch.cuda.current_stream(dev).synchronize()                   # the contract of QPS_MEM_DEVICE: the producing work has completed
+            args = [(None, 0) if v is None else (v.data_ptr(), v.numel()) for v in (vP, vA)]
+        else:
+            keep = tuple(None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for v in (vP, vA))
+            for v, name in zip(keep, ("vP", "vA")):
+                if v is not None and v.ndim != 1:
+                    raise ValueError(f"{name} must be a vector")
+            args = [(None, 0) if v is None else (v.ctypes.data, v.size) for v in keep]   # keep: alive until the call returns
+        (pP, kP), (pA, kA) = args
+        _lib.check(_lib.lib().qps_update_shared_values(self._h, pP, kP, pA, kA, _lib.QPS_MEM_DEVICE if device else _lib.QPS_MEM_HOST), self._h)
 
     def solve(self, mX=None, *, linsys="auto", **kw):
         """As ``QuadraticProgramSharedBatch.solve``; ``linsys`` ("auto" or "ldl": the sparse L D L' either way) goes to the library as it is."""
