@@ -391,6 +391,31 @@ int32_t qps_get_shared_certificate(qps_handle h, double *dy /* [count][m] or NUL
 int32_t qps_polish_shared(qps_handle h, double *x_inout, const double *y, const qps_params *params, qps_polish_report *reports);
 int32_t qps_set_shared_polish(qps_handle h, int32_t on /* 1: every qps_solve_batch ends with the step; 0 (default): as without it */);
 
+/* Adjoint derivatives of the solution on a shared-matrix batch handle (dense, sparse or CG): how a loss on x* changes with q, l, u and with the stored values of
+ * P and A -- OSQP's adjoint_derivative_compute / _get_vec / _get_mat, for every column at once.  Per column, from a solution x, the multipliers y and
+ * gx = dloss/dx: the active sets are those of the polishing step (L = {y_i < 0}, U = {y_i > 0}), K = [P, A_L', A_U'; A_L, 0, 0; A_U, 0, 0] is its reduced KKT
+ * matrix, and K r = [gx; 0] is solved by its refinement rounds (MINRES on K + blkdiag(delta I, -delta I), all columns in lockstep on 16-column panels, every
+ * column with its own state).  With r_lambda the multiplier block at full length m (zero outside the active sets):
+ *     dq = -r_x,      dl_i = r_lambda_i on L, else 0,      du_i = r_lambda_i on U, else 0,
+ *     dP_ij = -(r_x_i x_j + r_x_j x_i) / 2 for every stored entry of P (the gradient over symmetric perturbations: P is stored in full),
+ *     dA_ij = -(y_i r_x_j + r_lambda_i x_j) for every stored entry of A (exactly 0 on a row outside the active sets),
+ * dP and dA summed over the columns of the batch, since the columns share P and A.  dP_nzval and dA_nzval come in the order qps_get_shared_pattern hands out and
+ * qps_update_shared_values takes; they are accumulated in double, also on a QPS_F32 handle, in a fixed order: two runs agree bit for bit.  The step reads
+ * neither q, l nor u.  x and gx are [count][n]; y is [count][m], NULL takes the y the handle holds, as in qps_polish_shared.  The call uses numItrPolish, delta,
+ * epsMinres and numItrMinres of *params and nothing else of it, and leaves everything the handle keeps untouched -- stored z and y, factor, options,
+ * certificate: a following qps_solve_batch is bit for bit what it would have been.  A column whose last MINRES call ended with a flag other than 0 gets zeros in
+ * its rows of dq, dl, du and is left out of the sums dP, dA; reports[b].flag says so, and the other report fields have the meaning of qps_polish_report.
+ * Equilibration: the system is solved on the scaled data the handle holds, from D gx; r_x = D r~_x and r_lambda = E r~_lambda are exact powers of two, and
+ * every output is in the caller's units.  The derivatives hold while the active sets do not change.
+ * QPS_ERR_BAD_ARGUMENT: a NULL handle, x, gx or params, a NaN / Inf in x, y or gx, a delta that is not finite, a NaN epsMinres (before a device is needed; the
+ * handle is unchanged).  QPS_ERR_UNSUPPORTED (qps_last_error names the reason): any handle that is not a shared-matrix batch; a non-NULL dP_nzval or dA_nzval
+ * on a dense shared-matrix batch (dense matrix gradients are a panel GEMM: out of scope).
+ * Out of scope: results in device memory, stand-alone handles, qps_create_dense_batch, ProxQP handles, derivatives across a change of the active set. */
+int32_t qps_adjoint_shared(qps_handle h, const double *x, const double *y, const double *gx, const qps_params *params,
+                           double *dq, double *dl, double *du,    /* [count][n], [count][m], [count][m]; any may be NULL */
+                           double *dP_nzval, double *dA_nzval,    /* nnz(P), nnz(A) in the order of qps_get_shared_pattern; any may be NULL */
+                           qps_polish_report *reports);           /* [count] or NULL */
+
 /* Sparse shared-matrix batch: the same family of QPs on ONE sparse P (n x n, CSC, full symmetric storage) and ONE sparse A (m x n, CSC), index base 0 or 1
  * as for qps_create_csc -- a lasso / SVM regularisation path, a scenario sweep on a sparse model.  The linear system is the sparse L D L' of the KKT matrix
  * (QPS_LINSYS_KKT_LDL): ordering and symbolic factor are computed once, at creation, on the host (the QPS_LDL_* limits are read there, as a CSC handle reads

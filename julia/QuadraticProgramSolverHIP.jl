@@ -591,6 +591,32 @@ function SharedBatchPolish!(sb::SharedBatchHip, mX::Matrix{Float64}, mY::Union{N
     return vRep
 end
 
+# Adjoint derivatives of the solution of every column at once (qps_adjoint_shared): mGX (n x count) is the gradient of a loss with respect to the solutions mX
+# (n x count), mY (m x count) the multipliers, `nothing` takes the y the handle holds.  Returns (mDQ, mDL, mDU, vP, vA, vRep): mDQ n x count, mDL / mDU m x count per
+# column; vP / vA the gradients with respect to the stored values of P and A summed over the columns, in the order of the handle's canonical CSC pattern --
+# `nothing` unless numNzP / numNzA (the counts qps_get_shared_pattern reports) are given, which a dense shared-matrix batch refuses.  A column whose report has
+# flag != 0 has zero columns and is left out of vP / vA.  Nothing the handle keeps is touched.
+function SharedBatchAdjoint(sb::SharedBatchHip, mGX::Matrix{Float64}, mX::Matrix{Float64}, mY::Union{Nothing, Matrix{Float64}} = nothing; numItrPolish = 10,
+    δ = 1e-6, ϵMinres = 1e-6, numItrMinres = 500, numNzP::Union{Nothing, Integer} = nothing, numNzA::Union{Nothing, Integer} = nothing)
+    h = sb.h; count = sb.count
+    (size(mGX) == (sb.n, count) && size(mX) == (sb.n, count)) || throw(DimensionMismatch("mGX and mX must be n x count"))
+    (mY === nothing || size(mY) == (sb.m, count)) || throw(DimensionMismatch("mY must be m x count"))
+    prm = QpsParams(5000, 0, 25, numItrPolish, numItrMinres, 0, 0, 0, 1e-6, 1e-6, 1.0, 1e-6, 1.6, δ, 5.0, ϵMinres, 1e-6, 1000, 0, 0, 0)
+    buf = Vector{UInt8}(undef, count * sizeof(QpsPolishReport))
+    mDQ = zeros(sb.n, count); mDL = zeros(sb.m, count); mDU = zeros(sb.m, count)
+    vP = numNzP === nothing ? nothing : zeros(numNzP); vA = numNzA === nothing ? nothing : zeros(numNzA)
+    pY = mY === nothing ? Ptr{Float64}(C_NULL) : pointer(mY)
+    pP = vP === nothing ? Ptr{Float64}(C_NULL) : pointer(vP); pA = vA === nothing ? Ptr{Float64}(C_NULL) : pointer(vA)
+    GC.@preserve mGX mX mY mDQ mDL mDU vP vA buf _check(ccall((:qps_adjoint_shared, LIBQPS), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{QpsParams},
+                                                              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}),
+                                                              h, mX, pY, mGX, Ref(prm), mDQ, mDL, mDU, pP, pA, buf), h)
+    vRep = [QpsPolishReport() for _ in 1:count]
+    for b in 1:count
+        unsafe_copyto!(Ptr{UInt8}(pointer_from_objref(vRep[b])), pointer(buf, (b - 1) * sizeof(QpsPolishReport) + 1), sizeof(QpsPolishReport))
+    end
+    return mDQ, mDL, mDU, vP, vA, vRep
+end
+
 # on = true: every SharedBatchSolve! ends with the polishing step on its own x and y (qps_set_shared_polish); false (the default): as without it
 function SharedBatchSetPolish!(sb::SharedBatchHip, on::Bool = true)
     _check(ccall((:qps_set_shared_polish, LIBQPS), Int32, (Ptr{Cvoid}, Int32), sb.h, on ? 1 : 0), sb.h)

@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "qps_set_shared_adaptive_rho", "qps_set_shared_equilibration", "qps_get_shared_equilibration", "qps_set_shared_warm_start", "qps_set_shared_dual",
     "qps_set_shared_infeasibility", "qps_get_shared_certificate", "qps_polish_shared", "qps_set_shared_polish",
     "qps_create_csc_shared_batch_cg", "qps_update_shared_matrices", "qps_update_shared_matrices_csc", "qps_set_shared_column_rho",
-    "qps_get_shared_pattern", "qps_update_shared_values",
+    "qps_get_shared_pattern", "qps_update_shared_values", "qps_adjoint_shared",
 ]
 
 QPS_OK = 0
@@ -160,6 +160,7 @@ def lib() -> C.CDLL:
     L.qps_set_shared_infeasibility.argtypes = [hp, dbl, dbl]
     L.qps_get_shared_certificate.argtypes = [hp, dp, dp]
     L.qps_polish_shared.argtypes = [hp, dp, dp, C.POINTER(QpsParams), C.POINTER(QpsPolishReport)]
+    L.qps_adjoint_shared.argtypes = [hp, dp, dp, dp, C.POINTER(QpsParams), dp, dp, dp, dp, dp, C.POINTER(QpsPolishReport)]
     L.qps_set_shared_polish.argtypes = [hp, C.c_int32]
     L.qps_create_csc_shared_batch.argtypes = [i64, i64, i64, ip, ip, dp, ip, ip, dp, dp, dp, dp, i32, i32, i32, C.POINTER(hp)]
     L.qps_create_csc_shared_batch_cg.argtypes = [i64, i64, i64, ip, ip, dp, ip, ip, dp, dp, dp, dp, i32, i32, i32, C.POINTER(hp)]

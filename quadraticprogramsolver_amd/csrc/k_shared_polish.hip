@@ -86,6 +86,51 @@ __global__ __launch_bounds__(256) void k_sp_setup(G g, const T* __restrict__ q, 
         if (nu) atomicAdd(&counts[2 * (P * 16 + col) + 1], nu);
     }
 }
+// the set-up of qps_adjoint_shared, the twin of k_sp_setup: mask = (y < 0 || y > 0), g = [g_x ; 0], counts as there
+template <typename T>
+__global__ __launch_bounds__(256) void k_sp_adjoint_setup(G g, const T* __restrict__ gx, const T* __restrict__ y, T* __restrict__ mask, T* __restrict__ gv,
+                                                          int* __restrict__ counts) {
+    const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    int nl = 0, nu = 0;
+    for (int r = blockIdx.x * 16 + rl; r < g.rowsN + g.rowsM; r += gridDim.x * 16) {
+        const int64_t i = vec_index(g, P, r, col);
+        if (r < g.rowsN) { gv[i] = r < g.n ? gx[((int64_t)P * g.rowsN + r) * 16 + col] : T(0); continue; }
+        const int rm = r - g.rowsN;
+        const int64_t j = ((int64_t)P * g.rowsM + rm) * 16 + col;
+        T mk = T(0);
+        if (rm < g.m) {
+            const T yi = y[j];
+            if (yi < T(0)) { mk = T(1); ++nl; }
+            else if (yi > T(0)) { mk = T(1); ++nu; }
+        }
+        mask[j] = mk; gv[i] = T(0);
+    }
+    nl += __shfl_xor(nl, 16); nl += __shfl_xor(nl, 32);
+    nu += __shfl_xor(nu, 16); nu += __shfl_xor(nu, 32);
+    if ((threadIdx.x & 63) < 16) {                              // integer sums: any order gives the same count
+        if (nl) atomicAdd(&counts[2 * (P * 16 + col)], nl);
+        if (nu) atomicAdd(&counts[2 * (P * 16 + col) + 1], nu);
+    }
+}
+// the read-out of qps_adjoint_shared: dq = -t_x, dl = t_lambda where y < 0, du = t_lambda where y > 0; a column that is not live gives zeros and its t is
+// cleared, so that what sums over the columns afterwards leaves it out
+template <typename T>
+__global__ __launch_bounds__(256) void k_sp_adjoint_readout(G g, const int* __restrict__ live, const T* __restrict__ y, T* __restrict__ t, T* __restrict__ dq,
+                                                            T* __restrict__ dl, T* __restrict__ du) {
+    const int P = blockIdx.y, col = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const bool on = live[P * 16 + col] != 0;
+    for (int r = blockIdx.x * 16 + rl; r < g.rowsN + g.rowsM; r += gridDim.x * 16) {
+        const int64_t i = vec_index(g, P, r, col);
+        if (!on) t[i] = T(0);
+        const T v = on ? t[i] : T(0);
+        if (r < g.rowsN) { dq[((int64_t)P * g.rowsN + r) * 16 + col] = on ? -v : T(0); continue; }
+        const int rm = r - g.rowsN;
+        const int64_t j = ((int64_t)P * g.rowsM + rm) * 16 + col;
+        const T yi = rm < g.m ? y[j] : T(0);
+        dl[j] = yi < T(0) ? v : T(0);
+        du[j] = yi > T(0) ? v : T(0);
+    }
+}
 // wl = mask v_lambda (every column)
 template <typename T> __global__ __launch_bounds__(256) void k_sp_wl(G g, const T* __restrict__ mask, const T* __restrict__ v, T* __restrict__ wl) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, len = (int64_t)g.npanel * g.rowsM * 16;
@@ -259,6 +304,12 @@ template <typename T>
 void shared_polish_setup(hipStream_t st, const SharedPolishGeom& g, const T* q, const T* l, const T* u, const T* y, T* mask, T* gv, int* counts) {
     hipLaunchKernelGGL((k_sp_setup<T>), grid_of(g), dim3(256), 0, st, g, q, l, u, y, mask, gv, counts);
 }
+template <typename T> void shared_adjoint_setup(hipStream_t st, const SharedPolishGeom& g, const T* gx, const T* y, T* mask, T* gv, int* counts) {
+    hipLaunchKernelGGL((k_sp_adjoint_setup<T>), grid_of(g), dim3(256), 0, st, g, gx, y, mask, gv, counts);
+}
+template <typename T> void shared_adjoint_readout(hipStream_t st, const SharedPolishGeom& g, const int* live, const T* y, T* t, T* dq, T* dl, T* du) {
+    hipLaunchKernelGGL((k_sp_adjoint_readout<T>), grid_of(g), dim3(256), 0, st, g, live, y, t, dq, dl, du);
+}
 template <typename T> void shared_polish_wl(hipStream_t st, const SharedPolishGeom& g, const T* mask, const T* v, T* wl) {
     const int64_t len = (int64_t)g.npanel * g.rowsM * 16;
     hipLaunchKernelGGL((k_sp_wl<T>), dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st, g, mask, v, wl);
@@ -291,6 +342,8 @@ template <typename T> void shared_polish_select(hipStream_t st, const SharedPoli
 
 #define INST(T)                                                                                                                                              \
     template void shared_polish_setup<T>(hipStream_t, const SharedPolishGeom&, const T*, const T*, const T*, const T*, T*, T*, int*);                        \
+    template void shared_adjoint_setup<T>(hipStream_t, const SharedPolishGeom&, const T*, const T*, T*, T*, int*);                                         \
+    template void shared_adjoint_readout<T>(hipStream_t, const SharedPolishGeom&, const int*, const T*, T*, T*, T*, T*);                                    \
     template void shared_polish_wl<T>(hipStream_t, const SharedPolishGeom&, const T*, const T*, T*);                                                         \
     template void shared_polish_rhs<T>(hipStream_t, const SharedPolishGeom&, const int*, const T*, const T*, const SharedPolishProducts<T>&, T*);            \
     template void shared_polish_begin<T>(hipStream_t, const SharedPolishGeom&, const int*, T, const T*, const T*, const SharedPolishProducts<T>&, T*, T*, T*, \

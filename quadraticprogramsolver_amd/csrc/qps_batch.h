@@ -35,6 +35,10 @@ struct SharedFamilyOps {
     virtual void get_certificate(double* dy, double* dx) = 0;                             // [count][m], [count][n]; either may be NULL
     // qps_polish_shared: x [count][n] (replaced where reports[b].flag == 0), y [count][m] or NULL = the stored y, reports [count] or NULL; finite arrays
     virtual void polish(double* x, const double* y, const qps_params& p, qps_polish_report* reports) = 0;
+    // qps_adjoint_shared: x, gx [count][n], y [count][m] or NULL = the stored y, finite arrays; dq [count][n], dl, du [count][m], dP [nnz(P)], dA [nnz(A)] and
+    // reports [count] may each be NULL.  Nothing the handle keeps is written.
+    virtual void adjoint(const double* x, const double* y, const double* gx, const qps_params& p, double* dq, double* dl, double* du, double* dP, double* dA,
+                         qps_polish_report* reports) = 0;
     // qps_update_shared_matrices / qps_update_shared_matrices_csc: new values on the handle's pattern, everything else kept (options, q, l, u, z, y, analysis,
     // allocations); the numeric factor goes stale.  A path implements the form it was created from; the other form is refused with QPS_ERR_UNSUPPORTED before the
     // arrays are looked at (takes_csc() tells qps_capi.hip which).  A refused call leaves the handle bit for bit what it was; a returning call leaves the stream idle.

@@ -587,6 +587,23 @@ QPS_API int32_t qps_polish_shared(qps_handle hh, double* x, const double* y, con
     return guarded(h, [&] { fam->polish(x, y, *p, reports); });
 }
 
+QPS_API int32_t qps_adjoint_shared(qps_handle hh, const double* x, const double* y, const double* gx, const qps_params* p, double* dq, double* dl, double* du,
+                                   double* dP, double* dA, qps_polish_report* reports) {
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");
+    if (!x) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: x is NULL");
+    if (!gx) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: gx is NULL");
+    if (!p) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: params is NULL");
+    if (!std::isfinite(p->delta) || std::isnan(p->epsMinres)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: delta must be finite and epsMinres must not be NaN");
+    int rc; SharedFamilyOps* fam = shared_gate(h, "qps_adjoint_shared", "differentiate all columns at once", &rc);
+    if (!fam) return rc;
+    const int64_t c = h->fused_batch->count;
+    if (!all_finite(x, c * h->n, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: x contains NaN/Inf (the handle is unchanged)");
+    if (y && !all_finite(y, c * h->m, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: y contains NaN/Inf (the handle is unchanged)");
+    if (!all_finite(gx, c * h->n, false)) return fail_with(h, QPS_ERR_BAD_ARGUMENT, "qps_adjoint_shared: gx contains NaN/Inf (the handle is unchanged)");
+    return guarded(h, [&] { fam->adjoint(x, y, gx, *p, dq, dl, du, dP, dA, reports); });
+}
+
 QPS_API int32_t qps_set_shared_polish(qps_handle hh, int32_t on) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!h) return fail_with(nullptr, QPS_ERR_BAD_ARGUMENT, "handle is NULL");

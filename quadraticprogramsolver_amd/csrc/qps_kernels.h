@@ -236,6 +236,15 @@ void shared_polish_step(hipStream_t st, const SharedPolishGeom& g, SharedPolishS
                         T* c, T* r1, T* r2, T* w1, const T* w2, T* x, double* pa, double* pb);
 template <typename T> void shared_polish_add(hipStream_t st, const SharedPolishGeom& g, const int* live, const SharedPolishState* state, T* t, T* tt);   // t += tt (:319)
 template <typename T> void shared_polish_select(hipStream_t st, const SharedPolishGeom& g, const int* take, const T* t, T* x);   // x = t_x where take (:322-325)
+// qps_adjoint_shared, the second caller of the rounds: its set-up (mask and counts from the sign of y as above, g = [g_x; 0]) and its read-out (dq = -t_x,
+// dl / du = t_lambda on the rows with y < 0 / y > 0; a column that is not live gives zeros and its t is cleared)
+template <typename T> void shared_adjoint_setup(hipStream_t st, const SharedPolishGeom& g, const T* gx, const T* y, T* mask, T* gv, int* counts);
+template <typename T> void shared_adjoint_readout(hipStream_t st, const SharedPolishGeom& g, const int* live, const T* y, T* t, T* dq, T* dl, T* du);
+// k_value_gradient.hip: out[k] = scale * sum over the 16 npanel columns of  U[a] V[b] + W[b] Z[a]  for the nnz entries k of a CSR pattern, a = rowof[k], b = ci[k];
+// U, Z are panels [npanel][rowsA][16], V, W panels [npanel][rowsB][16].  Accumulated in double in a fixed order: independent of the grid, reproducible.
+template <typename T>
+void panel_value_gradient(hipStream_t st, int64_t nnz, const int* rowof, const int* ci, const T* U, const T* Z, int rowsA, const T* V, const T* W, int rowsB, int npanel,
+                          double scale, double* out);
 
 // ---- matrix-free CG of the shared-matrix batches (k_cg_panel.hip): LinOpCg! per column, all columns in lockstep on panels [npanel][n or m][16] ----------------
 // State: [2][16 npanel], ping-ponged by cg_panel_iteration (cur -> cur ^ 1); res2 / prev2 are the squared residual norms of cg!.  part_uc holds

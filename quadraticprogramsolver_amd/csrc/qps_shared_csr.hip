@@ -28,6 +28,9 @@ template <typename T> struct CsrFamilySolver : SharedFamilySolver<T> {
     // validate_values for P and for A on the device and pinned, and the three profiling categories of the call
     int* upd_partner = nullptr; unsigned long long *upd_verdict = nullptr, *h_verdict = nullptr;
     int cat_upd_stage = 0, cat_upd_check = 0, cat_upd_refresh = 0;
+    // qps_adjoint_shared, from its first call with a matrix gradient on: the row of every entry of the CSR copies P and A' (for both the column of the entry in
+    // the canonical CSC pattern), and the profiling category of the value kernel
+    int *adj_rowP = nullptr, *adj_rowAt = nullptr; int cat_adj_values = 0;
     const char* const path_word;   // "a sparse", "a CG": how the refusal of the dense form names the path
 
     CsrFamilySolver(int dev, int cnt, int64_t n_, int64_t m_, const char* word, std::vector<int64_t>&& Pcp, std::vector<int64_t>&& Pri, const std::vector<double>& Pnz,
@@ -177,6 +180,30 @@ template <typename T> struct CsrFamilySolver : SharedFamilySolver<T> {
     }
 
   protected:
+    // The CSR copy of P is in CSC order (symmetric, full storage) and the rows of A' are the columns of A, so both gradients come out in the canonical order
+    // without a map.  adj_rowP / adj_rowAt are built at the first call and kept, like upd_map; the two result arrays live for this call.
+    void value_gradients(const T* rx, const T* xv, const T* rl, const T* yv, double* dP, double* dA) override {
+        const int64_t np = nnzP(), na = nnzA();
+        if (!adj_rowP) {
+            const std::vector<int> rP = layout::csc_column_of_entry(n, hPcp), rA = layout::csc_column_of_entry(n, hAcp);
+            adj_rowP = mem.template dalloc<int>(np, st); adj_rowAt = mem.template dalloc<int>(na, st);
+            if (np > 0) up->copy(adj_rowP, rP.data(), sizeof(int) * (size_t)np);
+            if (na > 0) up->copy(adj_rowAt, rA.data(), sizeof(int) * (size_t)na);
+            // the two indices and the result per entry, the four panels once
+            cat_adj_values = prof.category("shared adjoint: value gradients of P and A", 16.0 * (np + na) + sizeof(T) * 16.0 * npanel * (2.0 * n + 2.0 * m));
+        }
+        DeviceOwner wm;
+        double* d = wm.dalloc<double>(np + na, st);
+        {
+            ProfScope ps(prof, cat_adj_values, 1);
+            if (dP && np > 0) panel_value_gradient<T>(st, np, adj_rowP, P.ci, rx, xv, (int)n, xv, rx, (int)n, npanel, -0.5, d);      // -(r_i x_j + r_j x_i) / 2
+            if (dA && na > 0) panel_value_gradient<T>(st, na, adj_rowAt, At.ci, rx, xv, (int)n, yv, rl, (int)m, npanel, -1.0, d + np);   // -(y_i r_j + rl_i x_j)
+        }
+        if (dP && np > 0) HIPC(hipMemcpyAsync(dP, d, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, st));
+        if (dA && na > 0) HIPC(hipMemcpyAsync(dA, d + np, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        prof.harvest();
+    }
     // QPS_MEM_DEVICE: "device memory, this device" by the pointer attributes, or QPS_ERR_BAD_ARGUMENT.  Host code only; nothing is enqueued.
     void require_device_memory(const char* name, const double* p) const {
         hipPointerAttribute_t at;

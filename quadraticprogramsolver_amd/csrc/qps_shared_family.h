@@ -348,35 +348,110 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
             r.numActiveUpper = pol[b].numUpper; r.reserved0 = 0; r.relres = pol[b].relres; r.seconds = pol[b].seconds;
         }
     }
+    // qps_adjoint_shared: per column, K r = [g_x; 0] on the active rows of y -- the system of the polishing step under another right-hand side, by the same
+    // refinement rounds -- then dq = -r_x, dl / du = r_lambda on the lower / upper active rows and, on a path that keeps a CSC pattern, the gradients with
+    // respect to the stored values of P and A summed over the columns (value_gradients).  With the equilibration on the rounds run on the scaled data: the
+    // right-hand side is D g_x, and r_x = D r~_x, r_lambda = E r~_lambda are exact; in the unscaled r, x, y every formula holds in the caller's units.  A column
+    // whose last MINRES call did not converge gives zeros and is left out of the sums.  Work panels of this call only; nothing the handle keeps is written.
+    void adjoint(const double* xh, const double* yh, const double* gxh, const qps_params& p, double* dq, double* dl, double* du, double* dPv, double* dAv,
+                 qps_polish_report* reports) override {
+        const bool mats = dPv || dAv;
+        if (mats && !this->takes_csc())
+            throw QpsError(QPS_ERR_UNSUPPORTED, "qps_adjoint_shared: a dense shared-matrix batch gives no gradients with respect to the matrices (dP_nzval and "
+                                                "dA_nzval must be NULL)");
+        HIPC(hipSetDevice(device));
+        const double t0 = now_s();
+        const int64_t pn = (int64_t)CP * rowsN, pm = (int64_t)CP * rowsM;
+        DeviceOwner wm;
+        T* gb = wm.dalloc<T>(pn, st); T* xb = mats ? wm.dalloc<T>(pn, st) : nullptr; T* yb = (yh || (mats && kd)) ? wm.dalloc<T>(pm, st) : nullptr;
+        T* out = wm.dalloc<T>(pn + 2 * pm, st);
+        put_panels(gxh, gb, n, rowsN);
+        if (kd) panel_rowscale<T>(st, gb, kd, 1, rowsN, npanel, gb);                                // D g_x
+        if (mats) put_panels(xh, xb, n, rowsN);                                                     // x and y stay in the caller's units: only the sign of y
+        if (yh) put_panels(yh, yb, m, rowsM);                                                       // enters the system, and E keeps it
+        else if (yb) panel_rowscale<T>(st, y, ke, 1, rowsM, npanel, yb);                            // y = E y~
+        const T* ypan = yb ? yb : y;
+        std::vector<PolishReport> reps(count, PolishReport());
+        PolishWork w;
+        polish_work_alloc(w, std::vector<int>());
+        shared_adjoint_setup<T>(st, w.g, gb, ypan, w.mask, w.gv, w.counts);
+        polish_fetch_counts(w);
+        polish_rounds(w, p, reps);
+        T* tl = w.t + pn;
+        if (kd) { panel_rowscale<T>(st, w.t, kd, 1, rowsN, npanel, w.t); panel_rowscale<T>(st, tl, ke, 1, rowsM, npanel, tl); }   // r_x = D r~_x, r_lambda = E r~_lambda
+        shared_adjoint_readout<T>(st, w.g, w.live_dev, ypan, w.t, out, out + pn, out + pn + pm);
+        if (dq) get_panels(out, dq, n, rowsN);
+        if (dl) get_panels(out + pn, dl, m, rowsM);
+        if (du) get_panels(out + pn + pm, du, m, rowsM);
+        if (mats) value_gradients(w.t, xb, tl, ypan, dPv, dAv);
+        HIPC(hipStreamSynchronize(st));
+        const double secs = now_s() - t0;
+        for (int b = 0; b < count && reports; ++b) {
+            qps_polish_report& r = reports[b];
+            r.flag = reps[b].flag; r.refinements = reps[b].refinements; r.minresIterations = reps[b].minresIterations; r.numActiveLower = w.hi[2 * b];
+            r.numActiveUpper = w.hi[2 * b + 1]; r.reserved0 = 0; r.relres = reps[b].relres; r.seconds = secs;
+        }
+    }
+    // The work panels of one run of the refinement rounds (polish_panels, adjoint): the KKT vectors gv (the right-hand side g), t (the solution) and the seven
+    // of MINRES, the mask and wl, the partial sums, the per-column states and counts and their pinned copies.  They live for one call.
+    struct PolishWork {
+        DeviceOwner wm;
+        SharedPolishGeom g;
+        T *gv = nullptr, *t = nullptr, *tt = nullptr, *rhs = nullptr, *c = nullptr, *r1 = nullptr, *r2 = nullptr, *w1 = nullptr, *w2 = nullptr, *mask = nullptr, *wl = nullptr;
+        double *pa = nullptr, *pb = nullptr; SharedPolishState *state = nullptr, *hs = nullptr; int *counts = nullptr, *live_dev = nullptr, *hi = nullptr;
+        std::vector<int> live; int nlive = 0;
+    };
+    void polish_work_alloc(PolishWork& w, const std::vector<int>& take) {
+        SharedPolishGeom& g = w.g; g.n = (int)n; g.m = (int)m; g.rowsN = rowsN; g.rowsM = rowsM; g.npanel = npanel;
+        const int64_t N = (int64_t)CP * (rowsN + rowsM), ML = (int64_t)CP * rowsM; const int nblk = shared_polish_blocks(rowsN, rowsM);
+        w.gv = w.wm.template dalloc<T>(9 * N + 2 * ML, st);
+        w.t = w.gv + N; w.tt = w.t + N; w.rhs = w.tt + N; w.c = w.rhs + N; w.r1 = w.c + N; w.r2 = w.r1 + N; w.w1 = w.r2 + N; w.w2 = w.w1 + N;   // t = tt = 0 (:307-308)
+        w.mask = w.w2 + N; w.wl = w.mask + ML;
+        w.pa = w.wm.template dalloc<double>(2 * (int64_t)CP * nblk, st); w.pb = w.pa + (int64_t)CP * nblk;
+        w.state = w.wm.template dalloc<SharedPolishState>(2 * (int64_t)CP, st);
+        w.counts = w.wm.template dalloc<int>(3 * (int64_t)CP, st); w.live_dev = w.counts + 2 * CP;
+        w.hs = w.wm.template pinned<SharedPolishState>((size_t)CP); w.hi = w.wm.template pinned<int>(3 * (size_t)CP);
+        w.live.assign(CP, 0);
+        w.nlive = 0;
+        for (int b = 0; b < count; ++b) w.nlive += w.live[b] = take.empty() || take[b];
+    }
+    void polish_push_live(PolishWork& w) {
+        for (int b = 0; b < CP; ++b) w.hi[2 * CP + b] = w.live[b];
+        HIPC(hipMemcpyAsync(w.live_dev, w.hi + 2 * CP, sizeof(int) * CP, hipMemcpyHostToDevice, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    // what follows the set-up kernel of either caller: the active-set counts on their way to the host, then the first mask of live columns
+    void polish_fetch_counts(PolishWork& w) {
+        HIPC(hipMemcpyAsync(w.hi, w.counts, sizeof(int) * 2 * CP, hipMemcpyDeviceToHost, st));
+        polish_push_live(w);
+    }
     // SolveQuadraticProgram.m:289-325 for the columns of `take` (empty: all), all at once, on the data the handle holds (the scaled data while the equilibration
-    // is on): ypan are rowsM panels, xpan rowsN panels that take t_x where the column's last MINRES call converged.  K v comes from check_products -- the
-    // matrices are read once per MINRES iteration for all columns of a panel pair -- and k_shared_polish.hip does the rest.  The columns advance in lockstep:
-    // in round jj those still refining form g - K t and run MINRES together, the host reading the per-column states every 8 iterations; a column whose call
-    // ended with flag 1 leaves with its x kept (:316-318), the others add tt and go on.  The work panels live for this call only.
+    // is on): ypan are rowsM panels, xpan rowsN panels that take t_x where the column's last MINRES call converged.  Three parts: the set-up of mask and
+    // right-hand side, the refinement rounds (polish_rounds) and the read-out.  The work panels live for this call only.
     void polish_panels(const T* ypan, T* xpan, const qps_params& p, const std::vector<int>& take, std::vector<PolishReport>& reps) {
         const double t0 = now_s();
         reps.assign(count, PolishReport());
         if (p.numItrPolish <= 0) return;                                                            // :292
-        SharedPolishGeom g; g.n = (int)n; g.m = (int)m; g.rowsN = rowsN; g.rowsM = rowsM; g.npanel = npanel;
-        const int64_t N = (int64_t)CP * (rowsN + rowsM), ML = (int64_t)CP * rowsM; const int nblk = shared_polish_blocks(rowsN, rowsM);
-        DeviceOwner wm;
-        T* gv = wm.dalloc<T>(9 * N + 2 * ML, st);
-        T *t = gv + N, *tt = t + N, *rhs = tt + N, *c = rhs + N, *r1 = c + N, *r2 = r1 + N, *w1 = r2 + N, *w2 = w1 + N, *mask = w2 + N, *wl = mask + ML;   // t = tt = 0 (:307-308)
-        double* pa = wm.dalloc<double>(2 * (int64_t)CP * nblk, st); double* pb = pa + (int64_t)CP * nblk;
-        SharedPolishState* state = wm.dalloc<SharedPolishState>(2 * (int64_t)CP, st);
-        int* counts = wm.dalloc<int>(3 * (int64_t)CP, st); int* live_dev = counts + 2 * CP;
-        SharedPolishState* hs = wm.pinned<SharedPolishState>((size_t)CP); int* hi = wm.pinned<int>(3 * (size_t)CP);
-        std::vector<int> live(CP, 0);
-        int nlive = 0;
-        for (int b = 0; b < count; ++b) nlive += live[b] = take.empty() || take[b];
-        auto push_live = [&] {
-            for (int b = 0; b < CP; ++b) hi[2 * CP + b] = live[b];
-            HIPC(hipMemcpyAsync(live_dev, hi + 2 * CP, sizeof(int) * CP, hipMemcpyHostToDevice, st));
-            HIPC(hipStreamSynchronize(st));
-        };
-        shared_polish_setup<T>(st, g, q, l, u, ypan, mask, gv, counts);                             // :293-299
-        HIPC(hipMemcpyAsync(hi, counts, sizeof(int) * 2 * CP, hipMemcpyDeviceToHost, st));
-        push_live();
+        PolishWork w;
+        polish_work_alloc(w, take);
+        shared_polish_setup<T>(st, w.g, q, l, u, ypan, w.mask, w.gv, w.counts);                     // :293-299
+        polish_fetch_counts(w);
+        polish_rounds(w, p, reps);
+        shared_polish_select<T>(st, w.g, w.live_dev, w.t, xpan);                                    // :322-325
+        HIPC(hipStreamSynchronize(st));
+        const double secs = now_s() - t0;
+        for (int b = 0; b < count; ++b) { reps[b].numLower = w.hi[2 * b]; reps[b].numUpper = w.hi[2 * b + 1]; reps[b].seconds = secs; }
+    }
+    // The refinement rounds :314-320 of K t = g from t = 0, for the mask and the right-hand side gv a set-up kernel left in `w`.  K v comes from check_products --
+    // the matrices are read once per MINRES iteration for all columns of a panel pair -- and k_shared_polish.hip does the rest.  The columns advance in lockstep:
+    // in round jj those still refining form g - K t and run MINRES together, the host reading the per-column states every 8 iterations; a column whose call
+    // ended with flag 1 leaves (:316-318), the others add tt and go on.  On return w.t holds t, and w.live / w.live_dev name the columns whose last call converged.
+    void polish_rounds(PolishWork& w, const qps_params& p, std::vector<PolishReport>& reps) {
+        const SharedPolishGeom& g = w.g;
+        T *const gv = w.gv, *const t = w.t, *const tt = w.tt, *const rhs = w.rhs, *const c = w.c, *const mask = w.mask, *const wl = w.wl;
+        T *r1 = w.r1, *r2 = w.r2, *w1 = w.w1, *w2 = w.w2;
+        double *const pa = w.pa, *const pb = w.pb; SharedPolishState *const state = w.state, *const hs = w.hs; int* const live_dev = w.live_dev;
+        std::vector<int>& live = w.live; int& nlive = w.nlive;
         const SharedPolishProducts<T> k{mask, wl, Ax, Px, Aty};
         const T delta = (T)p.delta;
         for (int jj = 0; jj < p.numItrPolish && nlive > 0; ++jj) {                                  // :314
@@ -411,15 +486,11 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
                 r.flag = s.done ? s.flag : 1; r.minresIterations += s.itn; r.refinements = jj + 1; r.relres = s.bnorm == 0.0 ? 0.0 : s.phibar / s.bnorm;
                 if (r.flag) { live[b] = 0; --nlive; }                                               // :316-318
             }
-            push_live();
+            polish_push_live(w);
             if (nlive > 0) shared_polish_add<T>(st, g, live_dev, state + (int64_t)cur * CP, t, tt); // :319
         }
         for (int b = 0; b < count; ++b) live[b] = reps[b].flag == 0;
-        push_live();
-        shared_polish_select<T>(st, g, live_dev, t, xpan);                                          // :322-325
-        HIPC(hipStreamSynchronize(st));
-        const double secs = now_s() - t0;
-        for (int b = 0; b < count; ++b) { reps[b].numLower = hi[2 * b]; reps[b].numUpper = hi[2 * b + 1]; reps[b].seconds = secs; }
+        polish_push_live(w);
     }
 
   protected:
@@ -435,6 +506,9 @@ template <typename T> struct SharedFamilySolver : BatchSolverBase, SharedFamilyO
     virtual void iterate(int lvl, double rho, double sigma, double alpha) = 0;        // one ADMM iteration of every active column, profiled at level `lvl`
     // Ax = A xv, Px = P xv, Aty = A'yv for arbitrary panels (the check's x, y; the certificates' dx, dyh; the polishing step's v_x, mask v_lambda); usable outside a solve
     virtual void check_products(const T* xv, const T* yv) = 0;
+    // qps_adjoint_shared on a path that keeps a CSC pattern: dP [nnz(P)] and dA [nnz(A)] (either may be null) in the order of that pattern, from the unscaled
+    // panels r_x, x (n rows) and r_lambda, y (m rows) whose padding columns and failed columns of r are zero.  Only such a path is ever asked.
+    virtual void value_gradients(const T* /*rx*/, const T* /*xv*/, const T* /*rl*/, const T* /*yv*/, double* /*dP*/, double* /*dA*/) {}
     virtual int64_t column_cg_iterations(int) { return 0; }                           // qps_info.cgIterations of column b of the running solve (a path without CG: 0)
     // set_rho_scale replaced the scale by `s` ([m], or NULL: none), stream idle: what the path keeps beside rs_rho / rs_rho1, and what it invalidates
     virtual void rho_scale_changed(const double* /*s*/) {}

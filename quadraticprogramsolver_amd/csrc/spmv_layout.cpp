@@ -104,6 +104,15 @@ std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::
     return map;
 }
 
+std::vector<int> csc_column_of_entry(int64_t ncols, const std::vector<int64_t>& cp) {
+    const int64_t nnz = cp[(size_t)ncols];
+    if (nnz > 2000000000LL || ncols > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");
+    std::vector<int> col((size_t)nnz);
+    for (int64_t j = 0; j < ncols; ++j)
+        for (int64_t k = cp[(size_t)j]; k < cp[(size_t)j + 1]; ++k) col[(size_t)k] = (int)j;
+    return col;
+}
+
 std::vector<int> csc_transpose_partner_map(int64_t n, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri) {
     const int64_t nnz = cp[(size_t)n];
     if (nnz > 2000000000LL || n > 2000000000LL) throw std::length_error("more than 2^31 non-zeros / rows / columns");

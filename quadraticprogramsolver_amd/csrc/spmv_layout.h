@@ -48,6 +48,9 @@ std::vector<int> csc_rows_position_map(int64_t nrows, int64_t ncols, const std::
 // Where the transpose partner of every entry of a canonical square CSC pattern is stored: entry k = (i, j) -> the position of (j, i), -1 where (j, i) is not
 // stored; a diagonal entry is its own partner.  What the symmetry test of a values-only update reads (qps_update_shared_values); the pattern alone decides it.
 std::vector<int> csc_transpose_partner_map(int64_t n, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri);
+// The column of every entry of a canonical CSC pattern, in storage order: entry k -> j with cp[j] <= k < cp[j + 1].  Read as the CSR of the transpose it is the
+// row of every entry: what the value gradients of qps_adjoint_shared index their panels with.
+std::vector<int> csc_column_of_entry(int64_t ncols, const std::vector<int64_t>& cp);
 // The CSC arrays of a canonical matrix (nrows x ncols) read as the CSR of its transpose (ncols x nrows) -- for a symmetric P that is P itself.
 CsrHost csc_as_transposed_csr(int64_t nrows, int64_t ncols, const std::vector<int64_t>& cp, const std::vector<int64_t>& ri, const std::vector<double>& nz);
 // [top; bottom] stacked (same column count)

@@ -452,6 +452,32 @@ class QuadraticProgramSharedBatch(_Handle):
         _lib.check(_lib.lib().qps_polish_shared(self._h, _dp(mX), None if y is None else _dp(y), C.byref(p), reps), self._h)
         return [r.as_dict() for r in reps]
 
+    _value_gradients = False   # the classes created from CSC arrays keep a pattern and give vP / vA
+
+    def adjoint(self, mGX, mX, mY=None, *, numItrPolish=10, δ=1e-6, ϵMinres=1e-6, numItrMinres=500, matrices=True):
+        """Adjoint derivatives of the solution for every column at once (qps_adjoint_shared; OSQP's ``adjoint_derivative_compute``): from ``mGX`` [count x n], the
+        gradient of a loss with respect to each column's solution, the solutions ``mX`` [count x n] and the multipliers ``mY`` [count x m] (``None`` takes the y
+        the handle holds), the gradient of that loss with respect to the data.  Per column the reduced KKT system of the polishing step on the active rows of y is
+        solved for the right-hand side [g_x; 0] by its refinement rounds.  Returns ``dict(dQ, dL, dU, vP, vA, reports)``: ``dQ`` [count x n], ``dL`` / ``dU``
+        [count x m] per column; ``vP`` / ``vA`` the gradients with respect to the stored values of ``mP`` (over symmetric perturbations) and ``mA``, summed over
+        the columns, in the order of ``pattern()`` and ``update_values`` -- ``None`` on the dense handle or with ``matrices=False``; ``reports`` as ``polish``.  A
+        column whose report has a flag other than 0 has zero rows and is left out of ``vP`` / ``vA``.  Nothing the handle keeps is touched; with equilibration
+        on, ``δ`` and ``ϵMinres`` act in the scaled variables and every result is in the caller's units."""
+        gx, x = self._rows(mGX, "mGX", self.n), self._rows(mX, "mX", self.n)
+        y = None if mY is None else self._rows(mY, "mY", self.m)
+        p = _lib.default_params()
+        p.numItrPolish, p.delta, p.epsMinres, p.numItrMinres = int(numItrPolish), float(δ), float(ϵMinres), int(numItrMinres)
+        dQ, dL, dU = np.zeros((self.count, self.n)), np.zeros((self.count, self.m)), np.zeros((self.count, self.m))
+        vP = vA = None
+        if matrices and self._value_gradients:
+            nP, nA = C.c_int64(), C.c_int64()
+            _lib.check(_lib.lib().qps_get_shared_pattern(self._h, C.byref(nP), C.byref(nA), None, None, None, None), self._h)
+            vP, vA = np.zeros(nP.value), np.zeros(nA.value)
+        reps = (_lib.QpsPolishReport * self.count)()
+        ptr = lambda a: None if a is None else _dp(a)
+        _lib.check(_lib.lib().qps_adjoint_shared(self._h, _dp(x), ptr(y), _dp(gx), C.byref(p), _dp(dQ), _dp(dL), _dp(dU), ptr(vP), ptr(vA), reps), self._h)
+        return dict(dQ=dQ, dL=dL, dU=dU, vP=vP, vA=vA, reports=[r.as_dict() for r in reps])
+
     def set_polish(self, on=True):
         """``True``: every ``solve`` ends with the polishing step on its own x and y (qps_set_shared_polish), with ``numItrPolish``, ``δ``, ``ϵMinres`` and
         ``numItrMinres`` of that ``solve``; ``polishFlag`` / ``polishIterations`` / ``tPolish`` of the info dicts report it per column, and a column that ended with
@@ -496,6 +522,7 @@ class QuadraticProgramSparseSharedBatch(QuadraticProgramSharedBatch):
     QPS_ERR_UNSUPPORTED; ``trsvBlock`` is accepted and without effect).  ``update``, ``solve`` and ``dual`` are those of ``QuadraticProgramSharedBatch``."""
 
     _create = "qps_create_csc_shared_batch"    # the entry point that takes the CSC arrays
+    _value_gradients = True
 
     def __init__(self, mP, mA, mQ, mL, mU, *, dtype="f64", device=0):
         if getattr(mP, "ndim", 0) != 2 or getattr(mA, "ndim", 0) != 2:
