@@ -90,7 +90,14 @@ typedef struct {
                                 1024 or 512 (fp64) / 2048 or 1024 (fp32) with n above it: blocked substitution, ONE launch per
                                 sweep (qps_info.sweepVariant = 5); other sizes below n: one launch per block phase (1)         */
     int32_t reuseFactor;     /* additive: 1 = keep the factorisation of a previous qps_solve/linsys_init when
-                                (rho, sigma) are unchanged; 0 = factorise on every call like the reference (:36)      */
+                                (rho, sigma) are unchanged; 0 = factorise on every call like the reference (:36).
+                                A dense fp64 handle (single QP, adptRho off, one inverted block; 2048 < n padded <= 4096, or
+                                n padded <= 8192 with QPS_WHITEN=1 at creation; QPS_WHITEN=0: never) then iterates in whitened coordinates u = inv(L) t, p = inv(L) x
+                                on B = A inv(L)' and G = inv(L) inv(L)', built once per factor inside that solve's tSetup (one
+                                more m x n and n x n matrix on the device); x = L p is formed at every check and at the end.
+                                Iterates and residuals agree with the classic loop to rounding (1e-12), not bit for bit, and
+                                the exact-fixed-point stall test at eps = 0 (|x - xp| <= 0, evaluated as |L (p - pp)|) may fire
+                                at a different iteration than in x coordinates                                               */
     double epsAbs;           /* ϵAbs 1e-6 */
     double epsRel;           /* ϵRel 1e-6 */
     double rho;              /* ρ 1 */

@@ -62,7 +62,7 @@ __device__ __forceinline__ void gemm_tile(int K, T alpha, const T* __restrict__ 
     // ktri 1: opB is lower triangular (opB(k,j) = 0 for k < j) -> start at k = j0;  ktri 2: opA is lower triangular
     // (opA(i,k) = 0 for k > i) -> stop after the diagonal tile of row block i0
     const int kbeg = (ktri == 1) ? j0 : (ktri == 3 ? i0 : 0);   // ktri 3: opA is upper triangular (opA(i,k) = 0 for k < i)
-    const int kend = (ktri == 2) ? min(K, i0 + GT) : K;
+    const int kend = (ktri == 2) ? min(K, i0 + GT) : (ktri == 4 ? min(K, j0 + GT) : K);   // ktri 4: opB is upper triangular (opB(k,j) = 0 for k > j)
     // opA(i0.., k0..) goes to As[k][i], opB(k0.., j0..) to Bs[k][j], 4 elements per thread each.  The slabs of the next GemmDepth k-steps are
     // in flight (in registers) while the current one is multiplied.
     T ga[GemmDepth<T>::v][4], gb[GemmDepth<T>::v][4];
@@ -967,7 +967,7 @@ void gemm(hipStream_t st, int M, int N, int K, T alpha, const T* A, int64_t lda,
     static const bool pair_ok = [] { const char* e = getenv("QPS_GEMM_PAIR"); return !(e && atoi(e) == 0); }();
     const int nj = N / GT, ni = M / GT;
     int pair = 0;
-    if (pair_ok && !lower_only && ktri != 0 && !(ak && bk) && (int64_t)ni * nj * batch >= 512) pair = (ktri == 1) ? (nj % 2 == 0) : (ni % 2 == 0);
+    if (pair_ok && !lower_only && ktri != 0 && ktri != 4 && !(ak && bk) && (int64_t)ni * nj * batch >= 512) pair = (ktri == 1) ? (nj % 2 == 0) : (ni % 2 == 0);
     dim3 grid(pair && ktri == 1 ? nj / 2 : nj, pair && ktri != 1 ? ni / 2 : ni, batch), block(256);
     // lower tiles of a square, chip-filling tile grid: 1-D grid in the XCD-aware order of lower_tile_of (QPS_GEMM_LOWER_MAP=0: the plain 2-D grid)
     static const bool map_ok = [] { const char* e = getenv("QPS_GEMM_LOWER_MAP"); return !(e && atoi(e) == 0); }();

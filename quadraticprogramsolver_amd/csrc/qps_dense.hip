@@ -3,6 +3,7 @@
 // Loop structure follows SolveQuadraticProgram.jl:36-73; the linear solve is the reduced form of
 // LinearSystemSolvers.jl:110-142 with cg! replaced by Cholesky + two triangular sweeps (ProxQP.jl:175-206,221-225).
 #include <memory>
+#include <type_traits>
 
 #include "dense_chol.h"
 #include "qps_batch.h"
@@ -62,10 +63,47 @@ template <typename T> struct DenseSolver : SolverBase {
     int prof_iter = 0;   // iteration index seen by the level-1 sampler (one bracketed launch per kernel kind per 50 iterations)
     int sample_lvl(int slot) const { return (prof.level == 1 && prof_iter % 50 == slot) ? 1 : 2; }
     int cat_atw, cat_colsum, cat_fwd, cat_bwd, cat_ax, cat_upd, cat_chk, cat_pass, cat_passchk, cat_sweep, cat_xsum, cat_small;
+    // Whitened two-launch iteration of solves on the cached factor (fp64; k_pass_w.hip): B = A W', G = W W' and the loop's vectors live in a block of their own,
+    // allocated and built at the first qualifying solve of a factor.  QPS_WHITEN (read here, at creation): 0 never, 1 wherever supported, unset: 2048 < NP <= 4096.
+    Arena warena;
+    T *wB = nullptr, *wG = nullptr, *wslab_e = nullptr, *wslab_g = nullptr, *wslab_y = nullptr;
+    T *wu = nullptr, *wp0 = nullptr, *wp1 = nullptr, *wc = nullptr, *wgd = nullptr, *wbty = nullptr, *wa = nullptr;
+    int whiten_mode = -1; bool whiten_valid = false, whiten_failed = false;
+    int cat_wpass, cat_wpasschk, cat_wsum, cat_wl;
+    bool whiten_wanted() const { return whiten_mode == 1 || (whiten_mode < 0 && NP > 2048 && NP <= 4096); }   // auto: the measured band (eager classic loop, four chunks per thread)
+    // B and G of the current factor (S lower = W: one inverted block).  false: the block could not be allocated, the handle stays on the classic loop.
+    bool whiten_build() {
+        if constexpr (std::is_same<T, double>::value) {
+            if (whiten_valid) return true;
+            if (whiten_failed) return false;
+            if (!wB) {
+                auto layout = [&](Arena& ar) {
+                    const int64_t sl = (int64_t)whitened_slabs() * NP;
+                    wB = ar.take<T>((int64_t)MP * NP); wG = ar.take<T>((int64_t)NP * NP);
+                    wslab_e = ar.take<T>(sl); wslab_g = ar.take<T>(sl); wslab_y = ar.take<T>(sl);
+                    wu = ar.take<T>(NP); wp0 = ar.take<T>(NP); wp1 = ar.take<T>(NP); wc = ar.take<T>(NP); wgd = ar.take<T>(NP); wbty = ar.take<T>(NP);
+                    wa = ar.take<T>(MP);
+                };
+                layout(warena);
+                const size_t need = warena.planned();
+                char* blk = nullptr;
+                if (hipMalloc((void**)&blk, need) != hipSuccess) { (void)hipGetLastError(); wB = nullptr; whiten_failed = true; return false; }
+                warena.base = blk; warena.bytes = need; warena.off = 0; warena.planning = false;
+                HIPC(hipMemsetAsync(blk, 0, need, st));
+                layout(warena);
+            }
+            tril_copy(st, S, tmp, NP);                                                            // W with zeros above the diagonal (tmp: free after factor())
+            gemm<T>(st, MP, NP, NP, T(1), A, NP, true, tmp, NP, true, T(0), wB, NP, false, 1, 0, 0, 0, 4);   // B[i][j] = sum_{k <= j} A[i][k] W[j][k]
+            gemm<T>(st, NP, NP, NP, T(1), tmp, NP, true, tmp, NP, true, T(0), wG, NP, true, 1, 0, 0, 0, 4);  // G[i][j] = sum_{k <= j} W[i][k] W[j][k], j <= i
+            whiten_valid = true;
+            return true;
+        } else return false;
+    }
 
     DenseSolver(int dev, int64_t n_, int64_t m_, int dt) {
         device = dev; n = n_; m = m_; dtype = dt;
         HIPC(hipSetDevice(device));
+        { const char* e = getenv("QPS_WHITEN"); whiten_mode = e ? atoi(e) : -1; }
         NP = roundup(n, 64); MP = roundup(m, 64);
         const int64_t nn = (int64_t)NP * NP;
         part_tiles = gemv_cols_tiles(MP);
@@ -117,6 +155,11 @@ template <typename T> struct DenseSolver : SolverBase {
         cat_sweep = prof.category("sweeps(fused fwd+bwd, triangle read once)", s * ((double)n * (n + 1) / 2 + 2.0 * n + (double)sweep_fused_slabs<T>(NP) * n));
         cat_xsum = prof.category("colsum(x~ slabs)", s * ((double)sweep_fused_slabs<T>(NP) * n + n));
         // single-launch small-problem loop: bytes PER ITERATION (one launch runs many; bench.py multiplies by the iterations it timed)
+        // whitened iteration: the stacked matrix [B ; tril(G)] once + u, gd, z, y, a, l, u in / out; the slab sum reads two slab sets
+        cat_wpass = prof.category("apass(fused A-pass; whitened, stacked with G)", s * ((double)m * n + (double)n * (n + 1) / 2 + 2.0 * n + 8.0 * m));
+        cat_wpasschk = prof.category("apass(check variant; whitened)", s * ((double)m * n + (double)n * (n + 1) / 2 + 2.0 * n + 8.0 * m));
+        cat_wsum = prof.category("wsum(whitened slab sums: p+, u+)", s * (2.0 * whitened_slabs() * n + 5.0 * n));
+        cat_wl = prof.category("lpass(x, x - xp, A'y: triangle of L once)", s * ((double)n * (n + 1) / 2 + 5.0 * n));
         cat_small = prof.category("admm_small(whole loop in one launch; bytes per iteration)", s * ((double)m * n + (double)n * n) + s * (6.0 * n + 10.0 * m));
     }
     ~DenseSolver() override {
@@ -148,7 +191,7 @@ template <typename T> struct DenseSolver : SolverBase {
     void factorize(double rho, double sigma, bool rebuild_all) {
         const bool rebuild = rebuild_all || !have_AA;
         const DenseChol<T> c = chol();
-        factor_valid = false;
+        factor_valid = false; whiten_valid = false;
         c.form(sigma, rho, rebuild, rebuild);                                                      // :112-114 / :128
         have_AA = true;
         c.factor(nb, 1, use_blocked());
@@ -228,6 +271,10 @@ template <typename T> struct DenseSolver : SolverBase {
         int convFlag = QPS_CONV_NUM_ITR;                                                            // :33
         const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma && fac_nb == nb && fac_premul == use_blocked();
         if (!reuse) factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma);        // :36
+        const bool small_path = small_ok && p.loopVariant == 0 && (NP + nb - 1) / nb == 1;
+        // whitened iteration: nothing was factorised in this call, fixed rho, the fused loop over one inverted block (S lower = inv(L)) would run
+        const bool whiten = reuse && whiten_wanted() && !p.adptRho && m > 0 && p.loopVariant != 1 && pass_slabs > 0 && !small_path && !fac_premul &&
+                            chol_sweep_variant<T>(NP, nb) != 1 && whitened_supported(NP, MP) && whiten_build();   // (built once per factor, inside tSetup)
         upload_vec(xh, x, n);
         HIPC(hipMemsetAsync(xp, 0, sizeof(T) * NP, st));                                            // :38
         HIPC(hipMemsetAsync(z, 0, sizeof(T) * std::max(MP, 64), st));                               // :39
@@ -251,7 +298,7 @@ template <typename T> struct DenseSolver : SolverBase {
             }
             return false;
         };
-        if (small_ok && p.loopVariant == 0 && (NP + nb - 1) / nb == 1) {
+        if (small_path) {
             // Small problem: the whole loop :45-71 runs inside one single-workgroup launch; the host only steps in for a rho switch.
             transpose_small<T>(st, A, NP, MP, At);
             int it = 0;
@@ -277,6 +324,64 @@ template <typename T> struct DenseSolver : SolverBase {
                 }
             }
             return finish(it, now_s(), 4);
+        }
+        if constexpr (std::is_same<T, double>::value) if (whiten) {
+            // Whitened coordinates: u = W t, p = W x, a = A x.  x is formed from p = inv(L) x at a check and at the end only (x = L p).
+            T *pc = wp0, *pn = wp1;                                                                 // current p, and the buffer the next one goes to
+            bool x0zero = true;
+            for (int64_t i = 0; i < n && x0zero; ++i) x0zero = xh[i] == 0.0;
+            if (x0zero) { HIPC(hipMemsetAsync(pc, 0, sizeof(T) * NP, st)); HIPC(hipMemsetAsync(wa, 0, sizeof(T) * MP, st)); }
+            else {
+                gemv_rows<T>(st, S, NP, x, pc, nullptr, T(1), T(0), 0, NP, 0, NP, 1);               // p0 = W x0
+                gemv_rows<T>(st, A, NP, x, wa, nullptr, T(1), T(0), 0, MP, 0, NP, 0);               // a0 = A x0
+            }
+            gemv_rows<T>(st, S, NP, q, wc, nullptr, T(1), T(0), 0, NP, 0, NP, 1);                   // c = W q
+            bool have_u = false;                                                                    // u of the next pass is formed (by a check's slab sum)
+            auto slab_sum = [&](bool first, bool with_bty) {
+                WhitenedSum<T> a;
+                a.slab_e = wslab_e; a.slab_g = wslab_g; a.slab_y = wslab_y; a.part_ld = NP; a.ntiles = whitened_slabs(); a.ncols = NP; a.first = first;
+                a.gd = wgd; a.p_old = pc; a.c = wc; a.p_new = pn; a.u = wu; a.bty = wbty; a.alpha = (T)alpha; a.sigma = (T)sigma;
+                { ProfLaunchScope ps(prof, cat_wsum, sample_lvl(29)); whitened_sum(st, with_bty, a); }
+                std::swap(pc, pn); have_u = true;
+            };
+            for (ii = 1; ii <= p.numIterations; ++ii) {                                             // :45
+                const bool check = (ii % p.numItrConv == 0);                                        // :63
+                prof_iter = ii;
+                if (!have_u) slab_sum(ii == 1, false);                                              // :57 and LinearSystemSolvers.jl:134-137, multiplied by W
+                if (check) HIPC(hipMemsetAsync(scratch, 0, 16 * sizeof(unsigned long long), st));
+                {
+                    WhitenedPass<T> a;
+                    a.B = wB; a.G = wG; a.ld = NP; a.NP = NP; a.MP = MP; a.u = wu; a.z = z; a.y = y; a.a = wa; a.l = l; a.hi = u;
+                    a.alpha = (T)alpha; a.rho = (T)rho; a.gd = wgd; a.slab_e = wslab_e; a.slab_g = wslab_g; a.slab_y = wslab_y; a.part_ld = NP; a.slots = scratch;
+                    const int lvl = (prof.level == 1 && (check || ii % 50 != 38)) ? 3 : 1;          // sampled as the classic pass is
+                    ProfLaunchScope ps(prof, check ? cat_wpasschk : cat_wpass, lvl);
+                    whitened_pass(st, check, a);                                                    // :59-61, :139, next :134-135; G u for :57
+                }
+                have_u = false;
+                if (check) {
+                    slab_sum(false, true);                                                          // pc = p of this iteration, pn = the previous one
+                    { ProfScope ps(prof, cat_wl, 2); whitened_lpass(st, M, NP, NP, pc, pn, wbty, x, Aty, scratch); }   // x, |x - xp|, mA' * vY
+                    {
+                        ProfScope ps(prof, cat_chk, 2);
+                        gemv_rows<T>(st, P, NP, x, Px, nullptr, T(1), T(0), 0, NP, 0, NP, 0);        // mP * vX
+                        CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
+                        check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs, 1);
+                    }
+                    HIPC(hipMemcpyAsync(res_host, res_dev, 15 * sizeof(double), hipMemcpyDeviceToHost, st));
+                    HIPC(hipStreamSynchronize(st));
+                    prof.harvest();
+                    resP = res_host[0]; resD = res_host[1]; rhorho = res_host[4]; convFlag = (int)res_host[5];
+                    if (convFlag != QPS_CONV_NUM_ITR) break;                                        // :66-68
+                }
+            }
+            const int done = ii > p.numIterations ? p.numIterations : ii;
+            if (done > 0) {
+                if (!have_u) slab_sum(false, false);
+                gemv_rows<T>(st, M, NP, pc, x, nullptr, T(1), T(0), 0, NP, 0, NP, 1);               // x = L p
+            }
+            HIPC(hipStreamSynchronize(st));
+            prof.harvest();
+            return finish(done, now_s(), sweep_variant());
         }
         const bool fused = pass_slabs > 0 && p.loopVariant != 1;
         int rhs_slabs = 0;   // z = y = 0: A'(rho z - y) = 0, no slab to add for the first right-hand side

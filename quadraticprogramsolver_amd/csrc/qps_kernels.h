@@ -110,6 +110,32 @@ template <typename T>
 int apass_proxqp(hipStream_t st, const T* G, int64_t ld, int NP, int MP, int me, const T* x, T* x_scratch, T* slack, T* dual,
                  const T* g, T rho, T* part, int64_t part_ld);
 
+// ---- whitened two-launch iteration of a dense fp64 handle on its cached factor (k_pass_w.hip) -------------------------------------
+// B = A W' (MP x NP, ld, padded like A), G = W W' (lower triangle read), u = W t; the pass streams [B ; tril(G)] once: z~ = B u with the z / y row updates
+// and a+ = alpha z~ + (1 - alpha) a (a = A x), slabs of B'(rho z - y), gd[r] = sum_{c <= r} G[r][c] u[c] and slabs of the strictly lower G'u;
+// check = true adds slabs of B'y and the primal-side norms (slots 0, 2, 3, 8) from a+ and z+.  Every slab set has whitened_slabs() rows.
+template <typename T> struct WhitenedPass {
+    const T *B = nullptr, *G = nullptr; int64_t ld = 0; int NP = 0, MP = 0, rows_per_wg = 0;
+    const T* u = nullptr; T *z = nullptr, *y = nullptr, *a = nullptr; const T *l = nullptr, *hi = nullptr;
+    T alpha = T(0), rho = T(1);
+    T *gd = nullptr, *slab_e = nullptr, *slab_g = nullptr, *slab_y = nullptr; int64_t part_ld = 0;
+    unsigned long long* slots = nullptr;
+};
+// g = gd + sum slab_g, p_new = alpha g + (1 - alpha) p_old, u = sigma p_new - c + sum slab_e, with_bty: bty = sum slab_y; first: p_new = p_old, u = sigma p_old - c
+template <typename T> struct WhitenedSum {
+    const T *slab_e = nullptr, *slab_g = nullptr, *slab_y = nullptr; int64_t part_ld = 0; int ntiles = 0, ncols = 0, first = 0;
+    const T *gd = nullptr, *p_old = nullptr, *c = nullptr; T *p_new = nullptr, *u = nullptr, *bty = nullptr;
+    T alpha = T(0), sigma = T(0);
+};
+bool whitened_supported(int NP, int MP);
+int whitened_slabs();
+void whitened_pass(hipStream_t st, bool check, WhitenedPass<double> a);
+void whitened_sum(hipStream_t st, bool with_bty, const WhitenedSum<double>& a);
+// x = L pn, slots[7] = max |L (pn - po)|, aty = L bty over the lower triangle of L, read once
+void whitened_lpass(hipStream_t st, const double* L, int64_t ld, int NP, const double* pn, const double* po, const double* bty, double* x, double* aty,
+                    unsigned long long* slots);
+void tril_copy(hipStream_t st, const double* S, double* D, int NP);   // D = lower triangle of S (NP x NP, ld NP), zeros above the diagonal
+
 // ---- fused triangular sweeps (k_trsv.hip) -----------------------------------------------------------------------------
 template <typename T> bool sweep_fused_supported(int NP);
 // Both sweeps fused into one pass over the lower triangle (single inverted block): slabs of x~ = W' (W t); the caller adds
@@ -332,7 +358,8 @@ void gemm(hipStream_t st, int M, int N, int K, T alpha, const T* A, int64_t lda,
           bool b_kcontig, T beta, T* C, int64_t ldc, bool lower_only, int batch = 1, int64_t sA = 0, int64_t sB = 0,
           int64_t sC = 0, int ktri = 0);
 // ktri: 1 = opB lower triangular (k loop starts at the tile's first column), 2 = opA lower triangular (k loop stops
-// after the tile's last row): structurally zero k-tiles are skipped.
+// after the tile's last row), 3 = opA upper triangular, 4 = opB upper triangular (k loop stops after the tile's last column): structurally zero
+// k-tiles are skipped.
 
 // M = PI + rho * AA (lower triangle incl. diagonal tiles; NP x NP)   (LinearSystemSolvers.jl:114,128)
 template <typename T> void assemble_M(hipStream_t st, int NP, const T* PI, const T* AA, T rho, T* M, int batch = 1,
