@@ -140,8 +140,9 @@ typedef struct {
                                 3 = explicit inverse, two triangular GEMVs, 4 = single-launch small-problem loop,
                                 5 = blocked substitution, ONE launch per sweep (n / trsvBlock dependent phases handed from workgroup to
                                     workgroup inside the launch; trsvBlock = 1024 or 512 fp64, 2048 or 1024 fp32); 0 otherwise */
-    int32_t sweepGaveUp;     /* times a variant-5 launch of this solve gave up waiting for its workgroups (only another PROCESS running the
-                                same kernel on the card can cause that) and the solve was repeated on variant 1; its time is in tLoop */
+    int32_t sweepGaveUp;     /* times a variant-5 launch of this solve gave up waiting for its workgroups (any concurrent work on the card
+                                can cause that, other streams of this process included) and the solve was repeated on variant 1; its time is in
+                                tLoop.  A variant-5 solve is bit-reproducible only when this is 0 */
     int32_t cgExplicit;      /* CSC handles, CG plugins: 1 = the solve ran cg! on the explicit reduced matrix (ItrSolCg, one product per CG iteration),
                                 0 = on the matrix-free operator (LinOpCg / LinMapsCg) or no CG at all */
 } qps_info;

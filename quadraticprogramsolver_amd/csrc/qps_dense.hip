@@ -5,7 +5,9 @@
 #include <memory>
 #include <type_traits>
 
+#include "admm_loop.h"
 #include "dense_chol.h"
+#include "dense_whitened.h"
 #include "qps_batch.h"
 #include "qps_internal.h"
 #include "qps_kernels.h"
@@ -63,47 +65,13 @@ template <typename T> struct DenseSolver : SolverBase {
     int prof_iter = 0;   // iteration index seen by the level-1 sampler (one bracketed launch per kernel kind per 50 iterations)
     int sample_lvl(int slot) const { return (prof.level == 1 && prof_iter % 50 == slot) ? 1 : 2; }
     int cat_atw, cat_colsum, cat_fwd, cat_bwd, cat_ax, cat_upd, cat_chk, cat_pass, cat_passchk, cat_sweep, cat_xsum, cat_small;
-    // Whitened two-launch iteration of solves on the cached factor (fp64; k_pass_w.hip): B = A W', G = W W' and the loop's vectors live in a block of their own,
-    // allocated and built at the first qualifying solve of a factor.  QPS_WHITEN (read here, at creation): 0 never, 1 wherever supported, unset: 2048 < NP <= 4096.
-    Arena warena;
-    T *wB = nullptr, *wG = nullptr, *wslab_e = nullptr, *wslab_g = nullptr, *wslab_y = nullptr;
-    T *wu = nullptr, *wp0 = nullptr, *wp1 = nullptr, *wc = nullptr, *wgd = nullptr, *wbty = nullptr, *wa = nullptr;
-    int whiten_mode = -1; bool whiten_valid = false, whiten_failed = false;
-    int cat_wpass, cat_wpasschk, cat_wsum, cat_wl;
-    bool whiten_wanted() const { return whiten_mode == 1 || (whiten_mode < 0 && NP > 2048 && NP <= 4096); }   // auto: the measured band (eager classic loop, four chunks per thread)
-    // B and G of the current factor (S lower = W: one inverted block).  false: the block could not be allocated, the handle stays on the classic loop.
-    bool whiten_build() {
-        if constexpr (std::is_same<T, double>::value) {
-            if (whiten_valid) return true;
-            if (whiten_failed) return false;
-            if (!wB) {
-                auto layout = [&](Arena& ar) {
-                    const int64_t sl = (int64_t)whitened_slabs() * NP;
-                    wB = ar.take<T>((int64_t)MP * NP); wG = ar.take<T>((int64_t)NP * NP);
-                    wslab_e = ar.take<T>(sl); wslab_g = ar.take<T>(sl); wslab_y = ar.take<T>(sl);
-                    wu = ar.take<T>(NP); wp0 = ar.take<T>(NP); wp1 = ar.take<T>(NP); wc = ar.take<T>(NP); wgd = ar.take<T>(NP); wbty = ar.take<T>(NP);
-                    wa = ar.take<T>(MP);
-                };
-                layout(warena);
-                const size_t need = warena.planned();
-                char* blk = nullptr;
-                if (hipMalloc((void**)&blk, need) != hipSuccess) { (void)hipGetLastError(); wB = nullptr; whiten_failed = true; return false; }
-                warena.base = blk; warena.bytes = need; warena.off = 0; warena.planning = false;
-                HIPC(hipMemsetAsync(blk, 0, need, st));
-                layout(warena);
-            }
-            tril_copy(st, S, tmp, NP);                                                            // W with zeros above the diagonal (tmp: free after factor())
-            gemm<T>(st, MP, NP, NP, T(1), A, NP, true, tmp, NP, true, T(0), wB, NP, false, 1, 0, 0, 0, 4);   // B[i][j] = sum_{k <= j} A[i][k] W[j][k]
-            gemm<T>(st, NP, NP, NP, T(1), tmp, NP, true, tmp, NP, true, T(0), wG, NP, true, 1, 0, 0, 0, 4);  // G[i][j] = sum_{k <= j} W[i][k] W[j][k], j <= i
-            whiten_valid = true;
-            return true;
-        } else return false;
-    }
+    // Whitened two-launch iteration of solves on the cached factor (fp64 only; dense_whitened.h).  Declared after `arena`: its block is freed before the lease goes.
+    std::conditional_t<std::is_same<T, double>::value, WhitenedState, NoWhitenedState> wh;
+    WhitenedView<T> whitened_view() const { return {st, NP, MP, A, S, tmp}; }
 
     DenseSolver(int dev, int64_t n_, int64_t m_, int dt) {
         device = dev; n = n_; m = m_; dtype = dt;
         HIPC(hipSetDevice(device));
-        { const char* e = getenv("QPS_WHITEN"); whiten_mode = e ? atoi(e) : -1; }
         NP = roundup(n, 64); MP = roundup(m, 64);
         const int64_t nn = (int64_t)NP * NP;
         part_tiles = gemv_cols_tiles(MP);
@@ -154,12 +122,8 @@ template <typename T> struct DenseSolver : SolverBase {
         // figure for the two separate sweeps it replaces is twice the triangle (bench.py reports that one as `two_sweep_algo_GBs`)
         cat_sweep = prof.category("sweeps(fused fwd+bwd, triangle read once)", s * ((double)n * (n + 1) / 2 + 2.0 * n + (double)sweep_fused_slabs<T>(NP) * n));
         cat_xsum = prof.category("colsum(x~ slabs)", s * ((double)sweep_fused_slabs<T>(NP) * n + n));
+        wh.categories(prof, (double)n, (double)m);
         // single-launch small-problem loop: bytes PER ITERATION (one launch runs many; bench.py multiplies by the iterations it timed)
-        // whitened iteration: the stacked matrix [B ; tril(G)] once + u, gd, z, y, a, l, u in / out; the slab sum reads two slab sets
-        cat_wpass = prof.category("apass(fused A-pass; whitened, stacked with G)", s * ((double)m * n + (double)n * (n + 1) / 2 + 2.0 * n + 8.0 * m));
-        cat_wpasschk = prof.category("apass(check variant; whitened)", s * ((double)m * n + (double)n * (n + 1) / 2 + 2.0 * n + 8.0 * m));
-        cat_wsum = prof.category("wsum(whitened slab sums: p+, u+)", s * (2.0 * whitened_slabs() * n + 5.0 * n));
-        cat_wl = prof.category("lpass(x, x - xp, A'y: triangle of L once)", s * ((double)n * (n + 1) / 2 + 5.0 * n));
         cat_small = prof.category("admm_small(whole loop in one launch; bytes per iteration)", s * ((double)m * n + (double)n * n) + s * (6.0 * n + 10.0 * m));
     }
     ~DenseSolver() override {
@@ -191,7 +155,7 @@ template <typename T> struct DenseSolver : SolverBase {
     void factorize(double rho, double sigma, bool rebuild_all) {
         const bool rebuild = rebuild_all || !have_AA;
         const DenseChol<T> c = chol();
-        factor_valid = false; whiten_valid = false;
+        factor_valid = false; wh.invalidate();
         c.form(sigma, rho, rebuild, rebuild);                                                      // :112-114 / :128
         have_AA = true;
         c.factor(nb, 1, use_blocked());
@@ -200,9 +164,10 @@ template <typename T> struct DenseSolver : SolverBase {
         c.check("P + sigma I + rho A'A", ctx, &f);
         factor_valid = true; fac_rho = rho; fac_sigma = sigma; fac_nb = nb; fac_premul = use_blocked();
     }
-    // Did a blocked-sweep launch give up waiting (its workgroups were not co-resident: only another PROCESS running the same kernel on the card
-    // can do that, launches of this process are chained by the sweep gate)?  Then the iterates are garbage: the caller repeats its work on the
-    // multi-launch sweeps (`blocked_off` until the next solve / linsys_init).  Synchronises the stream.
+    // Did a blocked-sweep launch give up waiting (its workgroups were not co-resident: ANY concurrent work on the card can do that, other streams of
+    // this process included -- the sweep gate chains the blocked sweeps only)?  Then the iterates are garbage: the caller repeats its work on the
+    // multi-launch sweeps (`blocked_off` until the next solve / linsys_init), so a blocked-sweep solve is bit-reproducible only when it reports
+    // sweepGaveUp == 0.  Synchronises the stream.
     bool sweep_gave_up(bool fetched = false) {
         if (!fac_premul) return false;
         unsigned* h = reinterpret_cast<unsigned*>(res_host + 14);
@@ -261,20 +226,30 @@ template <typename T> struct DenseSolver : SolverBase {
         }
         if (info) { info->sweepGaveUp = gave_up; info->cgExplicit = 0; info->tLoop += t_lost; }   // the repeated work is loop time
     }
+    // The three ADMM loops of a dense handle.  Each takes the loop state and returns what the epilogue reports.
+    enum class Route { Small, Whitened, Classic };
+    struct LoopEnd { int iterations; int variant; bool gave_up; };   // iterations done, qps_info.sweepVariant, a blocked sweep gave up (classic loop only)
+    // Small: the whole loop in one single-workgroup launch.  Whitened: nothing was factorised in this call, fixed rho, the fused loop over one inverted block
+    // (S lower = inv(L)) would run; B and G are built last, once per factor, when everything else holds (before the caller's t1: inside tSetup).  Neither of the
+    // two runs with `fac_premul` set (one sweep block / the condition below), so neither has to ask sweep_gave_up().
+    Route choose_route(const qps_params& p, bool reuse) {
+        const bool small_path = small_ok && p.loopVariant == 0 && (NP + nb - 1) / nb == 1;
+        const bool whiten = reuse && wh.wanted(NP) && !p.adptRho && m > 0 && p.loopVariant != 1 && pass_slabs > 0 && !small_path && !fac_premul &&
+                            chol_sweep_variant<T>(NP, nb) != 1 && whitened_supported(NP, MP) && wh.build(whitened_view());
+        return small_path ? Route::Small : whiten ? Route::Whitened : Route::Classic;
+    }
+    void drain() { HIPC(hipStreamSynchronize(st)); prof.harvest(); }
+    // the read-back of a check: 15 doubles, slot 14 carries the blocked sweeps' give-up word (abort_dev)
+    void fetch_check() { HIPC(hipMemcpyAsync(res_host, res_dev, 15 * sizeof(double), hipMemcpyDeviceToHost, st)); drain(); }
     bool solve_once(double* xh, const qps_params& p, qps_info* info) {
         if (p.linsys != QPS_LINSYS_AUTO && p.linsys != QPS_LINSYS_CHOLESKY)
             throw QpsError(QPS_ERR_UNSUPPORTED, "dense handles offer QPS_LINSYS_CHOLESKY only (qps_create_csc with dense_path = 0 for the CG and the sparse L D L' plugins)");
         const double t0 = now_s();
         nb = pick_nb<T>(p.trsvBlock, NP);
-        double rho = p.rho, sigma = p.sigma; const double alpha = p.alpha;
-        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;                                // SolveQuadraticProgram.jl:34
-        int convFlag = QPS_CONV_NUM_ITR;                                                            // :33
-        const bool reuse = p.reuseFactor && factor_valid && fac_rho == rho && fac_sigma == sigma && fac_nb == nb && fac_premul == use_blocked();
-        if (!reuse) factorize(rho, sigma, !p.reuseFactor || !have_AA || fac_sigma != sigma);        // :36
-        const bool small_path = small_ok && p.loopVariant == 0 && (NP + nb - 1) / nb == 1;
-        // whitened iteration: nothing was factorised in this call, fixed rho, the fused loop over one inverted block (S lower = inv(L)) would run
-        const bool whiten = reuse && whiten_wanted() && !p.adptRho && m > 0 && p.loopVariant != 1 && pass_slabs > 0 && !small_path && !fac_premul &&
-                            chol_sweep_variant<T>(NP, nb) != 1 && whitened_supported(NP, MP) && whiten_build();   // (built once per factor, inside tSetup)
+        AdmmLoop lp(p.rho);                                                                         // SolveQuadraticProgram.jl:33, :43
+        const bool reuse = p.reuseFactor && factor_valid && fac_rho == lp.rho && fac_sigma == p.sigma && fac_nb == nb && fac_premul == use_blocked();
+        if (!reuse) factorize(lp.rho, p.sigma, !p.reuseFactor || !have_AA || fac_sigma != p.sigma); // :36
+        const Route route = choose_route(p, reuse);
         upload_vec(xh, x, n);
         HIPC(hipMemsetAsync(xp, 0, sizeof(T) * NP, st));                                            // :38
         HIPC(hipMemsetAsync(z, 0, sizeof(T) * std::max(MP, 64), st));                               // :39
@@ -282,122 +257,117 @@ template <typename T> struct DenseSolver : SolverBase {
         HIPC(hipMemsetAsync(zp, 0, sizeof(T) * std::max(MP, 64), st));                              // :41
         HIPC(hipStreamSynchronize(st));
         const double t1 = now_s();
-        double rhorho = rho;                                                                        // :43
-        int ii = 0, nref = 0; double tref = 0, resP = NAN, resD = NAN;
-        // the end of both paths, `t_end` being when the loop ended: polish, download, report
-        auto finish = [&](int iterations, double t_end, int variant) {
-            PolishReport pr;
-            if (p.polish) polish_dense<T>(st, n, m, NP, MP, P, A, q, l, u, y, x, part, p, &pr);    // SolveQuadraticProgram.m:289-325
-            download_vec(x, xh, n);
-            if (info) {
-                info->convFlag = convFlag; info->iterations = iterations; info->numRefactor = nref; info->cgIterations = 0;
-                info->rhoFinal = rho; info->rhoProposed = rhorho; info->resPrim = resP; info->resDual = resD;
-                info->tSetup = t1 - t0; info->tLoop = t_end - t1; info->tRefactor = tref;
-                info->polishFlag = pr.flag; info->polishIterations = pr.minresIterations; info->tPolish = pr.seconds;
-                info->trsvBlock = nb; info->sweepVariant = variant;
+        LoopEnd end{};
+        switch (route) {
+        case Route::Small: end = loop_small(p, lp); break;
+        case Route::Whitened: if constexpr (std::is_same<T, double>::value) end = loop_whitened(xh, p, lp); break;
+        case Route::Classic: end = loop_classic(p, lp); break;
+        }
+        if (end.gave_up) return true;
+        finish(xh, p, info, lp, end, t1 - t0, now_s() - t1);
+        return false;
+    }
+    // the end of every route: polish, download, report (tLoop ended when the loop returned)
+    void finish(double* xh, const qps_params& p, qps_info* info, const AdmmLoop& lp, const LoopEnd& end, double tSetup, double tLoop) {
+        PolishReport pr;
+        if (p.polish) polish_dense<T>(st, n, m, NP, MP, P, A, q, l, u, y, x, part, p, &pr);        // SolveQuadraticProgram.m:289-325
+        download_vec(x, xh, n);
+        if (!info) return;
+        lp.fill_info(info, end.iterations, tSetup, tLoop, pr);
+        info->cgIterations = 0; info->trsvBlock = nb; info->sweepVariant = end.variant;
+    }
+    // Small problem: the whole loop :45-71 runs inside one single-workgroup launch; the host only steps in for a rho switch.
+    LoopEnd loop_small(const qps_params& p, AdmmLoop& lp) {
+        transpose_small<T>(st, A, NP, MP, At);
+        int it = 0;
+        while (it < p.numIterations) {
+            {
+                ProfScope ps(prof, cat_small, 1);   // events around the one launch (a ~3 us launch gap against a kernel of hundreds of us)
+                admm_small<T>(st, (int)n, (int)m, NP, MP, it, p.numIterations, p.numItrConv, p.adptRho, lp.rho, lp.rhorho, p.sigma, p.alpha, p.epsAbs,
+                              p.epsRel, eps_admm(p), p.fctrRho, A, At, P, S, q, l, u, x, xp, z, y, small_out);
             }
-            return false;
+            HIPC(hipMemcpyAsync(small_out_host, small_out, admm_small_out_bytes(), hipMemcpyDeviceToHost, st));
+            drain();
+            int last = 0, flag = 1, need = 0; double r8[8];
+            admm_small_read(small_out_host, &last, &flag, &need, r8);
+            it = last; lp.convFlag = flag; lp.rhorho = r8[4];
+            if (!std::isnan(r8[0]) || !std::isnan(r8[1])) { lp.resP = r8[0]; lp.resD = r8[1]; }
+            if (flag != QPS_CONV_NUM_ITR) break;                                                    // :66-68
+            if (need && it < p.numIterations) refactor_at_switch(lp, p.sigma);                      // :47-51 (the loop top is never re-entered after the last iteration)
+        }
+        return {it, 4, false};
+    }
+    void refactor_at_switch(AdmmLoop& lp, double sigma) {                                           // :48-51
+        lp.rho = lp.rhorho; ++lp.nref;
+        const double ta = now_s();
+        factorize(lp.rho, sigma, false);                                                            // changedΡ: LinearSystemSolvers.jl:127-129
+        lp.tref += now_s() - ta;
+    }
+    // Whitened coordinates: u = W t, p = W x, a = A x.  x is formed from p = inv(L) x at a check and at the end only (x = L p).
+    LoopEnd loop_whitened(const double* xh, const qps_params& p, AdmmLoop& lp) {
+        static_assert(std::is_same<T, double>::value, "the whitened kernels are fp64 only");
+        const WhitenedView<T> wv = whitened_view();
+        T *pc = wh.p0, *pn = wh.p1;                                                                 // current p, and the buffer the next one goes to
+        bool x0zero = true;
+        for (int64_t i = 0; i < n && x0zero; ++i) x0zero = xh[i] == 0.0;
+        if (x0zero) { HIPC(hipMemsetAsync(pc, 0, sizeof(T) * NP, st)); HIPC(hipMemsetAsync(wh.a, 0, sizeof(T) * MP, st)); }
+        else {
+            gemv_rows<T>(st, S, NP, x, pc, nullptr, T(1), T(0), 0, NP, 0, NP, 1);                   // p0 = W x0
+            gemv_rows<T>(st, A, NP, x, wh.a, nullptr, T(1), T(0), 0, MP, 0, NP, 0);                 // a0 = A x0
+        }
+        gemv_rows<T>(st, S, NP, q, wh.c, nullptr, T(1), T(0), 0, NP, 0, NP, 1);                     // c = W q
+        bool have_u = false;                                                                        // u of the next pass is formed (by a check's slab sum)
+        auto slab_sum = [&](bool first, bool with_bty) {
+            { ProfLaunchScope ps(prof, wh.cat_sum, sample_lvl(29)); whitened_sum(st, with_bty, wh.sum_args(NP, first, pc, pn, p.alpha, p.sigma)); }
+            std::swap(pc, pn); have_u = true;
         };
-        if (small_path) {
-            // Small problem: the whole loop :45-71 runs inside one single-workgroup launch; the host only steps in for a rho switch.
-            transpose_small<T>(st, A, NP, MP, At);
-            int it = 0;
-            while (it < p.numIterations) {
+        int ii;
+        for (ii = 1; ii <= p.numIterations; ++ii) {                                                 // :45
+            const bool check = (ii % p.numItrConv == 0);                                            // :63
+            prof_iter = ii;
+            if (!have_u) slab_sum(ii == 1, false);                                                  // :57 and LinearSystemSolvers.jl:134-137, multiplied by W
+            if (check) HIPC(hipMemsetAsync(scratch, 0, 16 * sizeof(unsigned long long), st));
+            {
+                const int lvl = (prof.level == 1 && (check || ii % 50 != 38)) ? 3 : 1;              // sampled as the classic pass is
+                ProfLaunchScope ps(prof, check ? wh.cat_passchk : wh.cat_pass, lvl);
+                whitened_pass(st, check, wh.pass_args(wv, z, y, l, u, p.alpha, lp.rho, scratch));   // :59-61, :139, next :134-135; G u for :57
+            }
+            have_u = false;
+            if (check) {
+                slab_sum(false, true);                                                              // pc = p of this iteration, pn = the previous one
+                { ProfScope ps(prof, wh.cat_l, 2); whitened_lpass(st, M, NP, NP, pc, pn, wh.bty, x, Aty, scratch); }   // x, |x - xp|, mA' * vY
                 {
-                    ProfScope ps(prof, cat_small, 1);   // events around the one launch (a ~3 us launch gap against a kernel of hundreds of us)
-                    admm_small<T>(st, (int)n, (int)m, NP, MP, it, p.numIterations, p.numItrConv, p.adptRho, rho, rhorho, sigma, alpha, p.epsAbs,
-                                  p.epsRel, epsAdmm, p.fctrRho, A, At, P, S, q, l, u, x, xp, z, y, small_out);
+                    ProfScope ps(prof, cat_chk, 2);
+                    gemv_rows<T>(st, P, NP, x, Px, nullptr, T(1), T(0), 0, NP, 0, NP, 0);            // mP * vX
+                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, check_scalars(p, lp), 1);
                 }
-                HIPC(hipMemcpyAsync(small_out_host, small_out, admm_small_out_bytes(), hipMemcpyDeviceToHost, st));
-                HIPC(hipStreamSynchronize(st));
-                prof.harvest();
-                int last = 0, flag = 1, need = 0; double r8[8];
-                admm_small_read(small_out_host, &last, &flag, &need, r8);
-                it = last; convFlag = flag; rhorho = r8[4];
-                if (!std::isnan(r8[0]) || !std::isnan(r8[1])) { resP = r8[0]; resD = r8[1]; }
-                if (flag != QPS_CONV_NUM_ITR) break;                                                // :66-68
-                if (need && it < p.numIterations) {                                                 // :47-51 (the loop top is never re-entered after the last iteration)
-                    rho = rhorho; ++nref;
-                    const double ta = now_s();
-                    factorize(rho, sigma, false);
-                    tref += now_s() - ta;
-                }
+                fetch_check();
+                lp.read_check(res_host);
+                if (lp.convFlag != QPS_CONV_NUM_ITR) break;                                         // :66-68
             }
-            return finish(it, now_s(), 4);
         }
-        if constexpr (std::is_same<T, double>::value) if (whiten) {
-            // Whitened coordinates: u = W t, p = W x, a = A x.  x is formed from p = inv(L) x at a check and at the end only (x = L p).
-            T *pc = wp0, *pn = wp1;                                                                 // current p, and the buffer the next one goes to
-            bool x0zero = true;
-            for (int64_t i = 0; i < n && x0zero; ++i) x0zero = xh[i] == 0.0;
-            if (x0zero) { HIPC(hipMemsetAsync(pc, 0, sizeof(T) * NP, st)); HIPC(hipMemsetAsync(wa, 0, sizeof(T) * MP, st)); }
-            else {
-                gemv_rows<T>(st, S, NP, x, pc, nullptr, T(1), T(0), 0, NP, 0, NP, 1);               // p0 = W x0
-                gemv_rows<T>(st, A, NP, x, wa, nullptr, T(1), T(0), 0, MP, 0, NP, 0);               // a0 = A x0
-            }
-            gemv_rows<T>(st, S, NP, q, wc, nullptr, T(1), T(0), 0, NP, 0, NP, 1);                   // c = W q
-            bool have_u = false;                                                                    // u of the next pass is formed (by a check's slab sum)
-            auto slab_sum = [&](bool first, bool with_bty) {
-                WhitenedSum<T> a;
-                a.slab_e = wslab_e; a.slab_g = wslab_g; a.slab_y = wslab_y; a.part_ld = NP; a.ntiles = whitened_slabs(); a.ncols = NP; a.first = first;
-                a.gd = wgd; a.p_old = pc; a.c = wc; a.p_new = pn; a.u = wu; a.bty = wbty; a.alpha = (T)alpha; a.sigma = (T)sigma;
-                { ProfLaunchScope ps(prof, cat_wsum, sample_lvl(29)); whitened_sum(st, with_bty, a); }
-                std::swap(pc, pn); have_u = true;
-            };
-            for (ii = 1; ii <= p.numIterations; ++ii) {                                             // :45
-                const bool check = (ii % p.numItrConv == 0);                                        // :63
-                prof_iter = ii;
-                if (!have_u) slab_sum(ii == 1, false);                                              // :57 and LinearSystemSolvers.jl:134-137, multiplied by W
-                if (check) HIPC(hipMemsetAsync(scratch, 0, 16 * sizeof(unsigned long long), st));
-                {
-                    WhitenedPass<T> a;
-                    a.B = wB; a.G = wG; a.ld = NP; a.NP = NP; a.MP = MP; a.u = wu; a.z = z; a.y = y; a.a = wa; a.l = l; a.hi = u;
-                    a.alpha = (T)alpha; a.rho = (T)rho; a.gd = wgd; a.slab_e = wslab_e; a.slab_g = wslab_g; a.slab_y = wslab_y; a.part_ld = NP; a.slots = scratch;
-                    const int lvl = (prof.level == 1 && (check || ii % 50 != 38)) ? 3 : 1;          // sampled as the classic pass is
-                    ProfLaunchScope ps(prof, check ? cat_wpasschk : cat_wpass, lvl);
-                    whitened_pass(st, check, a);                                                    // :59-61, :139, next :134-135; G u for :57
-                }
-                have_u = false;
-                if (check) {
-                    slab_sum(false, true);                                                          // pc = p of this iteration, pn = the previous one
-                    { ProfScope ps(prof, cat_wl, 2); whitened_lpass(st, M, NP, NP, pc, pn, wbty, x, Aty, scratch); }   // x, |x - xp|, mA' * vY
-                    {
-                        ProfScope ps(prof, cat_chk, 2);
-                        gemv_rows<T>(st, P, NP, x, Px, nullptr, T(1), T(0), 0, NP, 0, NP, 0);        // mP * vX
-                        CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
-                        check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs, 1);
-                    }
-                    HIPC(hipMemcpyAsync(res_host, res_dev, 15 * sizeof(double), hipMemcpyDeviceToHost, st));
-                    HIPC(hipStreamSynchronize(st));
-                    prof.harvest();
-                    resP = res_host[0]; resD = res_host[1]; rhorho = res_host[4]; convFlag = (int)res_host[5];
-                    if (convFlag != QPS_CONV_NUM_ITR) break;                                        // :66-68
-                }
-            }
-            const int done = ii > p.numIterations ? p.numIterations : ii;
-            if (done > 0) {
-                if (!have_u) slab_sum(false, false);
-                gemv_rows<T>(st, M, NP, pc, x, nullptr, T(1), T(0), 0, NP, 0, NP, 1);               // x = L p
-            }
-            HIPC(hipStreamSynchronize(st));
-            prof.harvest();
-            return finish(done, now_s(), sweep_variant());
+        const int done = iterations_done(ii, p.numIterations);
+        if (done > 0) {
+            if (!have_u) slab_sum(false, false);
+            gemv_rows<T>(st, M, NP, pc, x, nullptr, T(1), T(0), 0, NP, 0, NP, 1);                   // x = L p
         }
+        drain();
+        return {done, sweep_variant(), false};
+    }
+    static CheckScalars check_scalars(const qps_params& p, const AdmmLoop& lp) { return {p.epsAbs, p.epsRel, eps_admm(p), lp.rho, lp.rhorho, p.adptRho, lp.convFlag}; }
+    // The classic loop: fused (eager or replayed as graphs) or unfused.  Swaps the members x and xp; the roles persist into the next solve (iter_graph is keyed on them).
+    LoopEnd loop_classic(const qps_params& p, AdmmLoop& lp) {
+        const double sigma = p.sigma, alpha = p.alpha;
         const bool fused = pass_slabs > 0 && p.loopVariant != 1;
         int rhs_slabs = 0;   // z = y = 0: A'(rho z - y) = 0, no slab to add for the first right-hand side
         // Launch-bound sizes (an iteration of four to eight kernels lasts less than the host needs to enqueue it): replay graphs.
-        // Profiling brackets launches and stays eager.
-        static const int graph_env = [] { const char* e = getenv("QPS_GRAPH"); return e ? atoi(e) : -1; }();
-        // (the blocked sweeps take a fresh epoch argument per launch: no replay)
-        const bool use_graph = fused && prof.level == 0 && p.numItrConv >= 3 && !fac_premul && (graph_env >= 0 ? graph_env != 0 : NP <= 2048);
+        // Profiling brackets launches and stays eager.  (The blocked sweeps take a fresh epoch argument per launch: no replay.)
+        const bool use_graph = fused && prof.level == 0 && p.numItrConv >= 3 && !fac_premul && (graph_env() >= 0 ? graph_env() != 0 : NP <= 2048);
+        int ii;
         for (ii = 1; ii <= p.numIterations; ++ii) {                                                 // :45
-            bool changed = false;
-            if (p.adptRho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {          // :47
-                rho = rhorho; ++nref; changed = true;                                               // :48-51
-                const double ta = now_s();
-                factorize(rho, sigma, false);                                                       // changedΡ: LinearSystemSolvers.jl:127-129
-                tref += now_s() - ta;
-            }
+            const bool changed = lp.wants_rho_switch(p);                                            // :47
+            if (changed) refactor_at_switch(lp, sigma);
+            const double rho = lp.rho;
             const bool check = (ii % p.numItrConv == 0);                                            // :63
             if (use_graph && !changed && !check && rhs_slabs == pass_slabs) {
                 // the plain iterations up to the next check (an even number of them, so x / xp end in the same roles) as ONE graph launch
@@ -421,8 +391,7 @@ template <typename T> struct DenseSolver : SolverBase {
                     gemv_rows<T>(st, P, NP, x, Px, nullptr, T(1), T(0), 0, NP, 0, NP, 0);            // mP * vX
                     gemv_cols_partial<T>(st, A, NP, y, nullptr, T(1), T(0), part, NP, MP, NP);       // mA' * vY
                     colsum<T>(st, part, NP, part_tiles, nullptr, T(0), nullptr, T(0), Aty, NP);
-                    CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
-                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs);   // :64
+                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, check_scalars(p, lp));   // :64
                 }
             } else {
                 // Fused loop: the pass of iteration ii-1 already left the slabs of A'(rho z - y); after a rho switch they
@@ -451,23 +420,19 @@ template <typename T> struct DenseSolver : SolverBase {
                     ProfScope ps(prof, cat_chk, 2);
                     colsum<T>(st, part2, NP, pass_slabs, nullptr, T(0), nullptr, T(0), Aty, NP);     // mA' * vY
                     gemv_rows<T>(st, P, NP, x, Px, nullptr, T(1), T(0), 0, NP, 0, NP, 0);            // mP * vX
-                    CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
-                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs, 1);
+                    check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, check_scalars(p, lp), 1);
                 }
             }
             if (check) {
-                HIPC(hipMemcpyAsync(res_host, res_dev, 15 * sizeof(double), hipMemcpyDeviceToHost, st));
-                HIPC(hipStreamSynchronize(st));
-                prof.harvest();
-                if (sweep_gave_up(true)) return true;
-                resP = res_host[0]; resD = res_host[1]; rhorho = res_host[4]; convFlag = (int)res_host[5];
-                if (convFlag != QPS_CONV_NUM_ITR) break;                                            // :66-68
+                fetch_check();
+                if (sweep_gave_up(true)) return {0, 0, true};
+                lp.read_check(res_host);
+                if (lp.convFlag != QPS_CONV_NUM_ITR) break;                                         // :66-68
             }
         }
-        HIPC(hipStreamSynchronize(st));
-        prof.harvest();
-        if (sweep_gave_up()) return true;
-        return finish(ii > p.numIterations ? p.numIterations : ii, now_s(), sweep_variant());
+        drain();
+        if (sweep_gave_up()) return {0, 0, true};
+        return {iterations_done(ii, p.numIterations), sweep_variant(), false};
     }
     void polish(double* xh, const double* yh, const qps_params& p, qps_polish_report* rep) override {
         HIPC(hipSetDevice(device));
@@ -475,10 +440,7 @@ template <typename T> struct DenseSolver : SolverBase {
         PolishReport pr;
         polish_dense<T>(st, n, m, NP, MP, P, A, q, l, u, y, x, part, p, &pr);
         download_vec(x, xh, n);
-        if (rep) {
-            rep->flag = pr.flag; rep->refinements = pr.refinements; rep->minresIterations = pr.minresIterations;
-            rep->numActiveLower = pr.numLower; rep->numActiveUpper = pr.numUpper; rep->reserved0 = 0; rep->relres = pr.relres; rep->seconds = pr.seconds;
-        }
+        if (rep) to_c_report(pr, rep);
     }
     void get_dual(double* zh, double* yh) override {
         HIPC(hipSetDevice(device));

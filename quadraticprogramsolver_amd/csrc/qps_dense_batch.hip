@@ -1,6 +1,7 @@
 // qps_dense_batch.hip -- BatchedDenseSolver: the lock-step ADMM loop driver of a batch of independent dense QPs of one shape, behind make_dense_batch (qps_batch.h).
 #include <memory>
 
+#include "admm_loop.h"
 #include "dense_chol.h"
 #include "qps_batch.h"
 #include "qps_internal.h"
@@ -204,7 +205,7 @@ template <typename T> struct BatchedDenseSolver : BatchSolverBase {
             std::vector<int> changed;
             if (p.adptRho)
                 for (int b = 0; b < count; ++b)
-                    if (active[b] && ((rhorho[b] * p.fctrRho < rho[b]) || (rhorho[b] > p.fctrRho * rho[b]))) {   // :47
+                    if (active[b] && wants_rho_switch(p, rho[b], rhorho[b])) {                       // :47
                         rho[b] = rhorho[b]; ++nref[b]; changed.push_back(b);
                     }
             if (!changed.empty()) refactor_changed(changed, sigma, rho, rhorho, active, tref, rhs_slabs > 0, true);

@@ -224,6 +224,15 @@ struct Arena {
         HIPC(hipMemsetAsync(base, 0, need, st));   // on the handle's stream: ordered before everything the handle enqueues later
         off = 0; planning = false;
     }
+    // the same for a block the handle can do without: a refused hipMalloc is not thrown but cleared and answered with false, the arena stays in planning
+    bool try_commit(hipStream_t st) {
+        const size_t need = planned();
+        if (hipMalloc((void**)&base, need) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; }
+        bytes = need;
+        HIPC(hipMemsetAsync(base, 0, need, st));
+        off = 0; planning = false;
+        return true;
+    }
     Arena() = default;
     Arena(const Arena&) = delete;
     ~Arena() { if (base) (void)hipFree(base); }

@@ -4,6 +4,7 @@
 // state is the ADMM vectors, the plugin choice and the graph cache of the direct plugin's plain iteration.
 #include <algorithm>
 
+#include "admm_loop.h"
 #include "qps_internal.h"
 #include "qps_kernels.h"
 #include "qps_ldl.h"
@@ -133,31 +134,29 @@ template <typename T> struct SparseSolver : SolverBase {
     void solve(double* xh, const qps_params& p, qps_info* info) override {
         HIPC(hipSetDevice(device));
         const double t0 = now_s();
-        double rho = p.rho; const double sigma = p.sigma, alpha = p.alpha;
+        AdmmLoop lp(p.rho); const double sigma = p.sigma, alpha = p.alpha;
         cgp.eps_pcg = p.epsPcg; cgp.itr_pcg = p.numItrPcg;
-        const double epsAdmm = std::fmin(p.epsAbs, p.epsRel) * 1e-2;
-        int convFlag = QPS_CONV_NUM_ITR;
         if (p.linsys == QPS_LINSYS_CHOLESKY) throw QpsError(QPS_ERR_UNSUPPORTED, "CSR handles offer QPS_LINSYS_CG, QPS_LINSYS_CG_EXPLICIT and QPS_LINSYS_KKT_LDL (create with dense_path=1 for the reduced Cholesky path)");
-        plugin_kind = resolve_kind(p.linsys, rho, sigma, !p.reuseFactor);                           // SolveQuadraticProgram.jl:36 LinSysSolInit (incl. the factorisation)
+        plugin_kind = resolve_kind(p.linsys, lp.rho, sigma, !p.reuseFactor);                        // SolveQuadraticProgram.jl:36 LinSysSolInit (incl. the factorisation)
         mats.upload_vec(xh, x, n);
         const size_t nb_ = sizeof(T) * (size_t)(n + 64), mb_ = sizeof(T) * (size_t)(m + 64);
         HIPC(hipMemsetAsync(xp, 0, nb_, st)); HIPC(hipMemsetAsync(xx, 0, nb_, st));                 // LinOpCgInit: vXX = zeros (:147)
         HIPC(hipMemsetAsync(z, 0, mb_, st)); HIPC(hipMemsetAsync(y, 0, mb_, st)); HIPC(hipMemsetAsync(zp, 0, mb_, st));
         HIPC(hipStreamSynchronize(st));
         const double t1 = now_s();
-        double rhorho = rho; int ii = 0, nref = 0; double resP = NAN, resD = NAN, tref = 0;
+        int ii = 0;
         cgp.cg_total = 0; cgp.last_cg = 4;
         const int NPv = (int)n, MPv = (int)m;
-        static const int graph_env = [] { const char* e = getenv("QPS_GRAPH"); return e ? atoi(e) : -1; }();
-        const bool use_graph = plugin_kind == QPS_LINSYS_KKT_LDL && prof.level == 0 && graph_env != 0;
+        const bool use_graph = plugin_kind == QPS_LINSYS_KKT_LDL && prof.level == 0 && graph_env() != 0;
         bool ldl_rhs_ready = false;   // the fused post/update launch leaves the next right-hand side behind; stale after a rho switch
         double* const res_host = mats.check_host();
         for (ii = 1; ii <= p.numIterations; ++ii) {
-            if (p.adptRho && ((rhorho * p.fctrRho < rho) || (rhorho > p.fctrRho * rho))) {
-                rho = rhorho; ++nref;                                                               // matrix-free CG: nothing to rebuild
-                if (plugin_kind == QPS_LINSYS_CG && cgp.cg_explicit) { const double ta = now_s(); cgp.reduced_values(rho, sigma); tref += now_s() - ta; }   // changedΡ: LinearSystemSolvers.jl:127-129
-                if (plugin_kind == QPS_LINSYS_KKT_LDL) { const double ta = now_s(); kkt.prepare(rho, sigma, true); tref += now_s() - ta; ldl_rhs_ready = false; }   // changedΡ: numeric refactor only
+            if (lp.wants_rho_switch(p)) {
+                lp.rho = lp.rhorho; ++lp.nref;                                                      // matrix-free CG: nothing to rebuild
+                if (plugin_kind == QPS_LINSYS_CG && cgp.cg_explicit) { const double ta = now_s(); cgp.reduced_values(lp.rho, sigma); lp.tref += now_s() - ta; }   // changedΡ: LinearSystemSolvers.jl:127-129
+                if (plugin_kind == QPS_LINSYS_KKT_LDL) { const double ta = now_s(); kkt.prepare(lp.rho, sigma, true); lp.tref += now_s() - ta; ldl_rhs_ready = false; }   // changedΡ: numeric refactor only
             }
+            const double rho = lp.rho;
             if (plugin_kind == QPS_LINSYS_KKT_LDL && prof.level < 2) {
                 // direct plugin: sweeps + ONE launch for nu -> z~, the x / z / y updates and the next right-hand side (k_ldl_post_update)
                 if (use_graph && ldl_rhs_ready && ii % p.numItrConv != 0) {
@@ -180,14 +179,14 @@ template <typename T> struct SparseSolver : SolverBase {
                     mats.mul(mats.P, x, Px);
                     if (m > 0) mats.mul(mats.At, y, Aty);
                     else HIPC(hipMemsetAsync(Aty, 0, nb_, st));
-                    CheckScalars cs{p.epsAbs, p.epsRel, epsAdmm, rho, rhorho, p.adptRho, convFlag};
+                    CheckScalars cs{p.epsAbs, p.epsRel, eps_admm(p), rho, lp.rhorho, p.adptRho, lp.convFlag};
                     check_convergence<T>(st, (int)n, (int)m, Ax, Px, Aty, q, x, xp, z, zp, scratch, res_dev, cs);
                 }
                 HIPC(hipMemcpyAsync(res_host, res_dev, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
                 HIPC(hipStreamSynchronize(st));
                 prof.harvest();
-                resP = res_host[0]; resD = res_host[1]; rhorho = res_host[4]; convFlag = (int)res_host[5];
-                if (convFlag != QPS_CONV_NUM_ITR) break;
+                lp.read_check(res_host);
+                if (lp.convFlag != QPS_CONV_NUM_ITR) break;
             }
         }
         HIPC(hipStreamSynchronize(st));
@@ -196,13 +195,10 @@ template <typename T> struct SparseSolver : SolverBase {
         PolishReport pr;
         if (p.polish) polish_device(p, &pr);
         mats.download_vec(x, xh, n);
-        if (info) {
-            info->convFlag = convFlag; info->iterations = ii > p.numIterations ? p.numIterations : ii;
-            info->numRefactor = nref; info->cgIterations = (int)cgp.cg_total; info->rhoFinal = rho; info->rhoProposed = rhorho;
-            info->resPrim = resP; info->resDual = resD; info->tSetup = t1 - t0; info->tLoop = t2 - t1; info->tRefactor = tref;
-            info->trsvBlock = 0; info->sweepVariant = 0; info->sweepGaveUp = 0; info->cgExplicit = (plugin_kind == QPS_LINSYS_CG && cgp.cg_explicit) ? 1 : 0;
-            info->polishFlag = pr.flag; info->polishIterations = pr.minresIterations; info->tPolish = pr.seconds;
-        }
+        if (!info) return;
+        lp.fill_info(info, iterations_done(ii, p.numIterations), t1 - t0, t2 - t1, pr);
+        info->cgIterations = (int)cgp.cg_total; info->cgExplicit = (plugin_kind == QPS_LINSYS_CG && cgp.cg_explicit) ? 1 : 0;
+        info->trsvBlock = 0; info->sweepVariant = 0; info->sweepGaveUp = 0;
     }
     void get_dual(double* zh, double* yh) override {
         HIPC(hipSetDevice(device));
@@ -226,10 +222,7 @@ template <typename T> struct SparseSolver : SolverBase {
         PolishReport pr;
         polish_device(p, &pr);
         mats.download_vec(x, xh, n);
-        if (rep) {
-            rep->flag = pr.flag; rep->refinements = pr.refinements; rep->minresIterations = pr.minresIterations;
-            rep->numActiveLower = pr.numLower; rep->numActiveUpper = pr.numUpper; rep->reserved0 = 0; rep->relres = pr.relres; rep->seconds = pr.seconds;
-        }
+        if (rep) to_c_report(pr, rep);
     }
     // qps_operator_apply: one application of P / A / A' / [P; A] / the reduced operator (LinearSystemSolvers.jl:152-157) through the SpMV kernels the loop
     // uses for them; work buffers only (the CG plugin's cu, cc: n; tm: m; w: m), the solver state stays

@@ -8,7 +8,10 @@ times is bitwise equal.  Not a test.
                                                                                 # small CSC and a small sparse ProxQP handle; shared: of one small handle per
                                                                                 # kind of the shared-matrix batches): median microseconds per cycle
 
-The routes are those named in tests/loop_param_cases.py.  `--group sparse` covers the CSC handle instead -- the CG plugin on every product form, the explicit
+The routes are those named in tests/loop_param_cases.py, and the whitened route of a reused fp64 solve (handles created under QPS_WHITEN=1, cases of
+tests/whitened_cases.py): (200, 330) fresh and reused from x = 0 and from a non-zero start, to eps, polished, under adptΡ (which takes the classic loop) and after
+it, and (1100, 2130) with two chunks per row.  For reg, fused_eager, unfused, blocked_sweeps and the whitened reused solves one more solve runs at profiling level 2
+and its (category, launches) pairs are dumped as `<route>/launches`: the launch sequence per category is pinned beside the results.  `--group sparse` covers the CSC handle instead -- the CG plugin on every product form, the explicit
 reduced matrix, the direct KKT plugin, AUTO, polishing, the plugin calls, the five operators -- and the sparse ProxQP form.  `--group shared` covers the three
 handle kinds of the shared-matrix batches (dense Cholesky, sparse KKT L D L', matrix-free CG) on two small families each: fixed 50 iterations, to eps = 1e-6, rho
 scale, family rho, equilibration, both warm start modes, certificates, polishing at the end of a solve and as a call, update() + reuseFactor, the three forms of
@@ -50,7 +53,15 @@ def dump(q, path):
         out[tag + "/X"], out[tag + "/Z"], out[tag + "/Y"], out[tag + "/info"] = np.array(x), np.array(zy[0]), np.array(zy[1]), vals
         print(f"{tag:40s} " + " ".join(f"{k}={info[k]:g}" for k in ("convFlag", "iterations", "numRefactor", "sweepVariant", "polishFlag")), flush=True)
 
-    def single(tag, shape, dtype="f64", reps=1, **kw):
+    def launch_sequence(tag, h, x, **kw):
+        """One more solve with every launch bracketed: the (category, launches) pairs of kernel_times(), in the order the categories were registered."""
+        h.set_profiling(2)
+        h.solve(x, **kw)
+        out[tag + "/launches"] = np.array([f"{k['name']} x {k['launches']}" for k in h.kernel_times()])
+        h.set_profiling(0)
+        print(f"{tag:40s} " + "; ".join(out[tag + "/launches"]), flush=True)
+
+    def single(tag, shape, dtype="f64", reps=1, launches=False, **kw):
         n, m = shape
         P, qq, A, l, u = q.GenerateDenseBenchmarkQP(n, m, stream=21, feasible=True)
         base = dict(numIterations=400, ϵAbs=1e-6, ϵRel=1e-6, ρ=RHO)
@@ -60,19 +71,47 @@ def dump(q, path):
                 x = np.zeros(n); info = {}
                 h.solve(x, info=info, **dict(base, reuseFactor=(r > 0)))
                 put(f"{tag}.{dtype}" + (f".resolve{r}" if reps > 1 else ""), x, h.dual(), info)
+            if launches:
+                launch_sequence(f"{tag}.{dtype}", h, np.zeros(n), **base)
 
     for dtype in ("f64", "f32"):
         lv = dict(loopVariant=2) if dtype == "f32" else {}                 # (200, 330) fits the single launch in fp32
-        single("reg", (64, 128), dtype)
-        single("fused_eager", (200, 330), dtype, numItrConv=2, **lv)
+        single("reg", (64, 128), dtype, launches=True)
+        single("fused_eager", (200, 330), dtype, launches=True, numItrConv=2, **lv)
         single("fused_graph", (200, 330), dtype, **lv)
-    single("unfused", (200, 330), loopVariant=1)
-    single("blocked_sweeps", (1024, 512), trsvBlock=512, numIterations=100)
+    single("unfused", (200, 330), launches=True, loopVariant=1)
+    single("blocked_sweeps", (1024, 512), launches=True, trsvBlock=512, numIterations=100)
     single("adaptive_rho", (200, 330), adptΡ=True, fctrΡ=1.0, numItrConv=5, numIterations=60, ϵAbs=0.0, ϵRel=0.0)   # a re-factorisation at every check
     single("adaptive_rho_small", (64, 128), adptΡ=True, fctrΡ=1.0, numItrConv=5, numIterations=60, ϵAbs=0.0, ϵRel=0.0)
     single("reuse_factor", (200, 330), reps=2)
     single("polish", (200, 330), polish=True)
     single("polish_small", (64, 128), polish=True)
+
+    # the whitened route: fp64 handles created under QPS_WHITEN=1, solves on the cached factor at a fixed rho
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import whitened_cases as W
+    from loop_param_cases import api_kw
+
+    def whitened(tag, shape, solves, x0=None, launches=None):
+        """One handle, the solves (suffix, keywords) in turn, the first one fresh and the others with reuseFactor, each from x0 (zero when None)."""
+        P, qq, A, l, u = W.problem(shape)
+        with environment(QPS_WHITEN="1"):                                  # read when the handle is created
+            h = q.QuadraticProgram(P, qq, A, l, u)
+        with h:
+            for r, (sfx, kw) in enumerate(solves):
+                x = np.zeros(shape[0]) if x0 is None else np.array(x0); info = {}
+                h.solve(x, info=info, reuseFactor=(r > 0), **kw)
+                put(f"{tag}.{sfx}", x, h.dual(), info)
+            if launches:
+                launch_sequence(f"{tag}.reused", h, np.zeros(shape[0]) if x0 is None else np.array(x0), reuseFactor=True, **launches)
+
+    fixed = api_kw(W.fixed_k())                                            # 60 iterations, a check every 10, ϵ = 0
+    whitened("whitened", W.SHAPES[0], [("fresh", fixed), ("reused1", fixed), ("reused2", fixed), ("reused_polish", dict(fixed, polish=True)),
+                                       ("reused_adaptive_is_classic", dict(fixed, adptΡ=True)), ("reused_after_adaptive", fixed)], launches=fixed)
+    whitened("whitened_x0", W.SHAPES[0], [("fresh", fixed), ("reused1", fixed), ("reused2", fixed)], x0=W.start(W.SHAPES[0]))
+    whitened("whitened_to_eps", W.SHAPES[0], [("fresh25", api_kw(dict(W.TO_EPS, numIterations=25))), ("reused", api_kw(W.TO_EPS))])
+    two = api_kw(W.fixed_k(numIterations=20))                              # (1100, 2130): the smallest shape with more than one chunk per row
+    whitened("whitened_two_chunks", W.SHAPES[1], [("fresh", two), ("reused", two)], launches=two)
 
     # the plugin calls of a dense handle
     n, m = 200, 330
